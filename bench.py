@@ -2,7 +2,12 @@
 6-block/128-filter ResNet at 400 sims/move (configs[2]: 256 concurrent games per
 GPU), every game played to its end, one MI355X per rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up (seeded weights, code objects, the tuning caches of every batch
+bucket), plays W untimed move rounds, times the headline self-play, writes its last
+round's outputs if --dump-outputs is given, and prints the result line.  Every other
+measurement (the sub-legs below) runs only with --full, after the headline.
 
 N>1 is launched by the driver as torchrun (one process per GPU, RCCL).  Self-play
 shards by game: every rank plays its own 256 games (weak scaling, no collective
@@ -15,15 +20,24 @@ Dirichlet alpha 0.05 / eps 0.15 on the first 10 moves, temperature max(0, 1 - n/
 the batched HIP forward.  Every game runs until is_game_over(); the run ends when
 the last game does, so the shrinking batches of the tail are inside the timed
 region.  A "step" is one move round (every live game makes one move, 400
-simulations); `steps` is the number of rounds the generation took (its longest
-game), NOT --steps: the workload is fixed by the config, --steps K / --warmup W
-size the configs[1] forward sub-leg.  `roofline` is the persistent residual tower
+simulations) and `ms_per_step` the wall time of the timed rounds / their number.
+Without --steps, `steps` is the number of rounds the generation took (its longest
+game).  --steps K times exactly K move rounds of the same workload: the generation
+is cut after K rounds (max_moves = K), and if its last game ends sooner a fresh
+generation (new game seeds) plays the rounds that are left; --warmup W plays W such
+rounds (other seeds) untimed first.  With K below the shortest game every round has
+all 256 games live, so `value` is then the rate of full rounds, without the tail.
+Game seeds, weights and settings depend on the arguments alone, so --dump-outputs
+DIR (the last timed round's training examples of every game that moved in it, as
+DIR/<name>.npy) can be compared between two builds.  `roofline` is the persistent residual tower
 (`conv_tower`, the dominant kernel) over its launches INSIDE the self-play run:
 algorithmic FLOPs of the boards each launch evaluated / hipEvent device time of
 those launches on the stream they ran on.
 
-Sub-legs (extra keys): `selfplay_fp32` (the headline self-play again with the eval residual
-convs in fp32 MFMA, tuning key 19 = 0), `forward_b512` (configs[1]: K forwards of 512 boards
+Sub-legs (--full; extra keys, null in a plain run): `selfplay_generation` (with --steps: one
+whole generation to game end, the headline of a run without --steps), `selfplay_fp32` (the
+headline self-play again with the eval residual convs in fp32 MFMA, tuning key 19 = 0),
+`forward_b512` (configs[1]: K forwards of 512 boards after W untimed ones, resident
 in HBM, own roofline), `train` (configs[3] train step, 6x128, B=128/GPU, RCCL all-reduce
 at N>1), `pente_10x256` (configs[4]: Pente self-play with the 10x256 net at 800
 sims, 32 games per GPU played to their end, its 10x256 forward at B=512 and train
@@ -49,6 +63,7 @@ import torch
 
 METRIC = json.load(open(os.path.join(REPO, "BASELINE.json")))["metric"]
 BLOCKS, CHANNELS, BATCH = 6, 128, 512
+FWD_STEPS = 50                                           # configs[1] forwards of a --full run without --steps
 PEAK_F32_MFMA = 157.3e12                                 # MI355X_MICROARCH.md: FP32 matrix peak
 PEAK_F16_MFMA = 16 * PEAK_F32_MFMA                       # dense F16/BF16 MFMA (the guide: 16x the fp32 rate)
 # split-fp16 residual convs (key 19 = 1, the default): three fp16 MFMAs per fp32-equivalent
@@ -419,15 +434,35 @@ def visit_buckets(model, top):
 SP_GROUPS = int(os.environ.get("AZG_SP_GROUPS", "2"))   # pipelined search / evaluate groups
 
 
-def selfplay_run(model, game_class, G, S, max_moves, seeds, profile=True):
+GEN_SEED_STRIDE = 1_000_000   # game seeds of the k-th generation of a --steps run: seed + k * stride
+
+
+def selfplay_driver(model, game_class, G, S):
+    """The G-game self-play driver of selfplay_run (native search forests, pinned
+    int8-board evaluators, SP_GROUPS groups)."""
+    from mcts.native_mcts import NativeSelfPlay
+    return NativeSelfPlay(None, game_class, G, S, cpuct=SP_CPUCT, dirichlet_alpha=SP_ALPHA, epsilon=SP_EPS,
+                          apply_dirichlet_n_first_moves=SP_NOISE_MOVES, evaluator_factory=model.board_evaluator,
+                          groups=min(SP_GROUPS, G))
+
+
+def selfplay_run(model, game_class, G, S, max_moves, seeds, profile=True, steps=None, sp=None):
     """One self-play generation of G concurrent games (native search, pipelined
     int8-board evaluator, SP_GROUPS groups: the host searches one while the GPU
     evaluates the others; results are identical for any grouping) -> (driver, seconds,
-    profile, boards per class)."""
-    from mcts.native_mcts import NativeSelfPlay
-    sp = NativeSelfPlay(None, game_class, G, S, cpuct=SP_CPUCT, dirichlet_alpha=SP_ALPHA, epsilon=SP_EPS,
-                        apply_dirichlet_n_first_moves=SP_NOISE_MOVES, evaluator_factory=model.board_evaluator,
-                        groups=min(SP_GROUPS, G))
+    profile, boards per class, results of the last generation).
+
+    steps: play exactly that many move rounds instead: the generation is cut after
+    `steps` rounds (max_moves = steps); if its last game ends sooner, a fresh generation
+    (seeds + GEN_SEED_STRIDE per generation) goes on for the rounds that are left.  The
+    driver's statistics then cover all of them, sp.rounds is their sum (= steps) and
+    sp.last_rounds the rounds of the last generation.  sp: a driver to reuse (its
+    statistics are reset)."""
+    if sp is None:
+        sp = selfplay_driver(model, game_class, G, S)
+    sp.boards = sp.forwards = sp.max_batch = sp.moves = sp.rounds = 0
+    sp.nn_seconds = sp.search_seconds = 0.0
+    sp.game_lengths = []
     eng = model.engine
     eng.clear_status()
     eng.tower_diag_clear()
@@ -441,7 +476,18 @@ def selfplay_run(model, game_class, G, S, max_moves, seeds, profile=True):
         if now - last[0] > 20.0:
             last[0] = now
             log(f"  {live} games live, {sp.moves} moves, {sp.boards} leaf boards, {now - t0:.0f} s")
-    results = sp.play(sp_temp, max_moves=max_moves, use_symmetries=True, seeds=seeds, progress=progress)
+    rounds, left, gen = 0, steps, 0
+    while True:
+        done = len(sp.game_lengths)
+        results = sp.play(sp_temp, max_moves=max_moves if left is None else min(max_moves, left),
+                          use_symmetries=True, seeds=[s + GEN_SEED_STRIDE * gen for s in seeds], progress=progress)
+        sp.last_rounds = max(sp.game_lengths[done:])
+        rounds += sp.last_rounds
+        if left is None or left <= sp.last_rounds:
+            break
+        left -= sp.last_rounds
+        gen += 1
+    sp.rounds = rounds
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof = eng.profile_read() if profile else {}
@@ -470,6 +516,33 @@ def tower_waits(eng) -> dict:
     return out
 
 
+def dump_outputs(out_dir, results, last_round):
+    """--dump-outputs: what the last timed move round computed, as a caller of
+    NativeSelfPlay.play receives it: of every game that moved in that round (its
+    `last_round`-th move) the position's 8 training examples (the dihedral images of
+    the encoded state and of the search policy pi, and the outcome z), in game order.
+    float32 arrays, 256 games: 7.4 MB.  Game seeds, weights and settings are functions
+    of the arguments alone, so two builds can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx, state, pi, z, winner = [], [], [], [], []
+    for g, (ex, w) in enumerate(results):
+        n = 8                                        # images per position (use_symmetries)
+        if len(ex) != n * last_round:                # the game ended in an earlier round
+            continue
+        tail = ex[-n:]
+        idx.append(g)
+        state.append(np.stack([e[0] for e in tail]))
+        pi.append(np.stack([e[1] for e in tail]))
+        z.append([e[2] for e in tail])
+        winner.append(w)
+    np.save(os.path.join(out_dir, "game_index.npy"), np.asarray(idx, np.float64))
+    np.save(os.path.join(out_dir, "state.npy"), np.asarray(state, np.float32))
+    np.save(os.path.join(out_dir, "pi.npy"), np.asarray(pi, np.float32))
+    np.save(os.path.join(out_dir, "z.npy"), np.asarray(z, np.float32))
+    np.save(os.path.join(out_dir, "winner.npy"), np.asarray(winner, np.float64))
+    log(f"wrote the last round's outputs of {len(idx)} games to {out_dir}")
+
+
 PRETRAIN_STEPS = 20
 
 
@@ -493,19 +566,27 @@ def pretrain(model, dev, steps=PRETRAIN_STEPS, batch=128):
     model.net.eval()
 
 
-def selfplay_leg(model, args, rank, world, dist, dev, local):
-    """configs[2] headline: G games x S sims/move per rank, every game to its end."""
+def selfplay_leg(model, args, rank, world, dist, dev, local, steps=None, warmup=0, dump=None):
+    """configs[2] headline: G games x S sims/move per rank, every game to its end, or
+    (steps) exactly `steps` move rounds after `warmup` untimed ones of the same size.
+    dump: a directory for the last timed round's outputs (dump_outputs)."""
     from games.gomoku import Gomoku
     G, S = args.sp_games, args.sp_sims
     model.net.eval()
     warm_seeds = [10_000 + i for i in range(8)]
     selfplay_run(model, Gomoku, 8, 64, 2, warm_seeds, profile=False)       # code objects, pinned pools
     visit_buckets(model, (G + 1) // 2 * 32)
+    sp = selfplay_driver(model, Gomoku, G, S)
+    if warmup > 0:
+        selfplay_run(model, Gomoku, G, S, args.sp_max_moves, [500_000 + 1000 * rank + i for i in range(G)],
+                     profile=False, steps=warmup, sp=sp)
     barrier_sync(dist, local)
-    log(f"self-play: {G} games x {S} sims/move to game end")
+    log(f"self-play: {G} games x {S} sims/move " + ("to game end" if steps is None else f"for {steps} move rounds"))
     sp, dt, prof, boards, results = selfplay_run(model, Gomoku, G, S, args.sp_max_moves,
-                                                 [1000 * rank + i for i in range(G)])
+                                                 [1000 * rank + i for i in range(G)], steps=steps, sp=sp)
     barrier_sync(dist, local)
+    if dump and rank == 0:
+        dump_outputs(dump, results, sp.last_rounds)
     n_boards, n_moves, n_games, n_ex = reduce_(dist, dev, [float(sp.boards), float(sp.moves), float(G),
                                                            float(sum(len(ex) for ex, _ in results))])
     dt_max, rounds_max = reduce_(dist, dev, [dt, float(sp.rounds)], op="max")
@@ -518,7 +599,8 @@ def selfplay_leg(model, args, rank, world, dist, dev, local):
         "boards_per_s": n_boards / dt_max, "moves_per_s": n_moves / dt_max, "games": int(n_games),
         "examples": int(n_ex),
         "detail": {
-            "moves_per_game": "to game end (is_game_over(), max_moves 225)",
+            "moves_per_game": ("to game end (is_game_over(), max_moves 225)" if steps is None else
+                               f"{steps} move rounds (--steps): generations cut at max_moves = the rounds left"),
             "game_length_rank0": {"mean": round(float(lengths.mean()), 1), "min": int(lengths.min()),
                                   "max": int(lengths.max())},
             "winners_rank0": winners,
@@ -539,7 +621,7 @@ def selfplay_leg(model, args, rank, world, dist, dev, local):
 
 
 def selfplay_fp32_leg(model, args, rank, world, dist, dev, local, sp):
-    """The headline self-play (same games, sims, seeds) with the eval residual convs in fp32
+    """The headline self-play (same games, sims, seeds, move rounds) with the eval residual convs in fp32
     MFMA (tuning key 19 = 0): what the split-fp16 arithmetic buys end to end, and the rate
     a caller gets who keeps the fp32 chain's numerics."""
     import _native
@@ -548,7 +630,7 @@ def selfplay_fp32_leg(model, args, rank, world, dist, dev, local, sp):
     try:
         G = args.sp32_games
         a = argparse.Namespace(**{**vars(args), "sp_games": G})
-        r = selfplay_leg(model, a, rank, world, dist, dev, local)
+        r = selfplay_leg(model, a, rank, world, dist, dev, local, steps=args.steps, warmup=args.warmup)
     finally:
         lib.azg_pv_set_tuning(19, prev)
     log(f"fp32 self-play done: {r['boards_per_s']:.0f} boards/s over {r['seconds']:.1f} s")
@@ -568,7 +650,7 @@ def forward_leg(model, args, rank, world, dist, dev, local, blocks=BLOCKS, ch=CH
     """configs[1] (and the configs[4] network): `steps` forwards of B synthetic boards
     resident in HBM; roofline of the residual tower from hipEvents."""
     from synth import synth_encoded
-    steps = args.steps if steps is None else steps
+    steps = (args.steps or FWD_STEPS) if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     eng = model.engine
     x = torch.from_numpy(synth_encoded(B, seed=1234 + rank)).to(dev)
@@ -699,8 +781,17 @@ def pente_leg(args, rank, world, dist, dev, local):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50, help="forwards of the configs[1] sub-leg")
-    ap.add_argument("--warmup", type=int, default=10, help="untimed forwards before the configs[1] sub-leg")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed move rounds of the self-play (default: one whole generation, every game to its "
+                         "end); with --full also the forwards of the configs[1] sub-leg")
+    ap.add_argument("--warmup", type=int, default=10,
+                    help="untimed move rounds of the same self-play before the timed ones; with --full also the "
+                         "untimed forwards before the configs[1] sub-leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the sub-legs: configs[1] forward, a whole generation (with "
+                         "--steps), fp32 self-play, configs[3] train, configs[4] 10x256 / Pente, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed move round computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-game-seconds", type=float, default=12.0,
                     help="wall-time bound per configs[0] CPU game (1 thread and all cores)")
@@ -721,6 +812,10 @@ def main():
                     help="seeded train_batch steps on synthetic data before the legs (SURVEY §8(d); 0: raw init)")
     ap.add_argument("--tune", action="append", default=[], help="KEY=VALUE tuning key (A/B and profiling runs)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.sp_games <= 0 and not args.full:
+        ap.error("--sp-games 0 (no headline: sub-legs only) needs --full")
     if args.tune:
         import _native
         lib = _native.load_library()
@@ -739,31 +834,34 @@ def main():
     if args.pretrain_steps > 0:
         pretrain(model, dev, args.pretrain_steps)
 
-    fwd = sp = None
-    if not args.skip_forward:
-        log("configs[1] forward leg")
-        fwd = forward_leg(model, args, rank, world, dist, dev, local)
-    sp32 = None
+    # the headline first, on the model as set up: a plain run does nothing else
+    fwd = sp = gen = sp32 = train = big = cpu = None
     if args.sp_games > 0:
-        sp = selfplay_leg(model, args, rank, world, dist, dev, local)
+        sp = selfplay_leg(model, args, rank, world, dist, dev, local, steps=args.steps, warmup=args.warmup,
+                          dump=args.dump_outputs)
         log(f"self-play done: {sp['boards_per_s']:.0f} boards/s over {sp['seconds']:.1f} s")
-        if args.sp32_games > 0:
+    if args.full:
+        if not args.skip_forward:
+            log("configs[1] forward leg")
+            fwd = forward_leg(model, args, rank, world, dist, dev, local)
+        if sp is not None and args.steps is not None:
+            # the headline of a run without --steps: one whole generation, every game to its end
+            gen = selfplay_leg(model, args, rank, world, dist, dev, local)
+            log(f"whole generation done: {gen['boards_per_s']:.0f} boards/s over {gen['seconds']:.1f} s")
+            gen = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in gen.items()}
+        if sp is not None and args.sp32_games > 0:
             sp32 = selfplay_fp32_leg(model, args, rank, world, dist, dev, local, sp)
-    train = None
-    if args.train_steps > 0:
-        log("configs[3] train leg")
-        train = train_leg(model, args, rank, world, dist, dev, local)
-    big = None
-    if args.big_steps > 0:
-        log("configs[4] 10x256 legs")
-        del model
-        torch.cuda.empty_cache()
-        big = pente_leg(args, rank, world, dist, dev, local)
-
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        log("cpu baseline (reference CPU path on the host)")
-        cpu = cpu_baseline(args.cpu_game_seconds)
+        if args.train_steps > 0:
+            log("configs[3] train leg")
+            train = train_leg(model, args, rank, world, dist, dev, local)
+        if args.big_steps > 0:
+            log("configs[4] 10x256 legs")
+            del model
+            torch.cuda.empty_cache()
+            big = pente_leg(args, rank, world, dist, dev, local)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            log("cpu baseline (reference CPU path on the host)")
+            cpu = cpu_baseline(args.cpu_game_seconds)
 
     if rank != 0:
         dist.destroy_process_group()
@@ -774,6 +872,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    span = ("every game played to its end (train.py:360-412)" if args.steps is None else
+            f"{args.steps} move rounds (--steps) after {args.warmup} untimed ones")
     out = {
         "metric": METRIC,
         "value": round(sp["boards_per_s"], 1),
@@ -789,16 +889,18 @@ def main():
         "data": (f"synthetic (self-play from the empty board; 6x128 weights = seeded init + {args.pretrain_steps} "
                  f"train_batch steps on synthetic boards / pi / z, SURVEY §8(d); no checkpoint)"),
         "config": {"workload": f"configs[2]: {args.sp_games} concurrent self-play games/GPU x {args.sp_sims} "
-                               f"sims/move, 15x15 Gomoku, 6-block/128-filter ResNet, every game played to its end "
-                               f"(train.py:360-412); value = NN-evaluated leaf boards / wall time of the whole "
-                               f"generation incl. its tail",
-                   "step": "one move round (every live game makes one move); steps = rounds of the generation",
-                   "moves_per_game": "to game end",
+                               f"sims/move, 15x15 Gomoku, 6-block/128-filter ResNet, {span}; "
+                               f"value = NN-evaluated leaf boards / wall time of the timed rounds"
+                               + (" (the whole generation incl. its tail)" if args.steps is None else ""),
+                   "step": "one move round (every live game makes one move); steps = timed rounds"
+                           + (" = rounds of the generation" if args.steps is None else " = --steps"),
+                   "moves_per_game": "to game end" if args.steps is None else f"{args.steps} rounds",
                    "games_per_gpu": args.sp_games, "sims_per_move": args.sp_sims, "net": f"{BLOCKS}x{CHANNELS}",
                    "global_batch": "leaf batch varies: up to 32 x games per forward",
                    "parallelism": f"replicas{world} (games shard by GPU; no collective in the timed region)"},
         "roofline": sp["roofline"],
         "selfplay": {k: v for k, v in sp.items() if k != "roofline"},
+        "selfplay_generation": gen,
         "selfplay_fp32": sp32,
         "forward_b512": fwd,
         "train": train,

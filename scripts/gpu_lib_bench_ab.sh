@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/lib_bench_ab
 mkdir -p $O
 : > $O/summary.txt
-F="--no-cpu-baseline --sp32-games 0 --train-steps 0 --big-steps 0 --pente-moves 0"
+F="--full --no-cpu-baseline --sp32-games 0 --train-steps 0 --big-steps 0 --pente-moves 0"
 for r in 1 2; do
   for lib in prev cur; do
     if [ $lib = prev ]; then L=alphazero-gomoku_amd/libazg_pv_prev.so; else L=alphazero-gomoku_amd/libazg_pv.so; fi
