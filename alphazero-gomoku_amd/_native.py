@@ -76,6 +76,8 @@ _SIGS = {
     "azg_pv_grad_count": (ctypes.c_int64, [_P]),
     "azg_pv_train_fp32_once": (ctypes.c_int32, [_P]),
     "azg_pv_posted": (ctypes.c_int32, [_P, ctypes.c_uint32]),
+    "azg_pv_replay_gather": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_CLASSES = ("conv3x3", "stem", "heads", "train_conv", "train_wgrad", "train_other", "tower", "tower16", "board",

@@ -84,6 +84,20 @@ int main()
     CHECK(azg_pv_last_seq(nullptr) == 0);
     CHECK(azg_pv_tower_diag_clear(nullptr, nullptr) != 0);
     CHECK(azg_pv_bind(nullptr, nullptr, nullptr, nullptr) != 0);
+    // replay gather: every argument is checked before any device call
+    {
+        int8_t st = 0;
+        float f = 0.f;
+        int64_t id = 0;
+        CHECK(azg_pv_replay_gather(nullptr, &f, &f, 4, 0, 2, 8, &id, 1, &f, &f, &f, nullptr) != 0);
+        CHECK(std::strlen(azg_pv_last_error()) > 0);
+        CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 2, 3, &id, 1, &f, &f, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 2, 8, &id, 0, &f, &f, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather(&st, &f, &f, 0, 0, 1, 8, &id, 1, &f, &f, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 5, 8, &id, 1, &f, &f, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 4, 2, 8, &id, 1, &f, &f, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 2, 8, nullptr, 1, &f, &f, &f, nullptr) != 0);
+    }
     // tuning keys round-trip (previous value returned)
     const int prev = azg_pv_set_tuning(5, 0);
     CHECK(azg_pv_set_tuning(5, prev) == 0);

@@ -1,0 +1,73 @@
+// Replay-buffer gather (include/azg_pv.h azg_pv_replay_gather): training batches from a
+// device-resident ring of canonical positions.  Each position is stored once as int8
+// stones (0 empty, 1 side to move, 2 opponent) + fp32 pi + fp32 z; a batch element is
+// one of its dihedral images, encoded on the fly:
+//   planes  <- Gomoku.get_encoded_state (games/gomoku.py:130-150)
+//   image s <- MCTS.symmetries (mcts/new_mcts_alpha.py:42-56): np.rot90 by k = s / 2
+//              (counter-clockwise), then a column flip when s is odd.
+// Every output value is a copy or a 0/1 constant: the result equals numpy's bit for bit.
+#include "pv_internal.h"
+
+namespace azg {
+
+// Source square of output square (y, x) under symmetry s: with r = np.rot90(a, k),
+// r[y][x] = a[x][n-1-y] for k = 1 (and its powers); np.flip(r, columns)[y][x] = r[y][n-1-x].
+__device__ __forceinline__ int replay_src(int y, int x, int s)
+{
+    constexpr int n = BOARD;
+    if (s & 1) x = n - 1 - x;
+    switch (s >> 1) {
+    case 0: return y * n + x;
+    case 1: return x * n + (n - 1 - y);
+    case 2: return (n - 1 - y) * n + (n - 1 - x);
+    default: return (n - 1 - x) * n + y;
+    }
+}
+
+// One 256-thread workgroup per sample; thread j < 225 owns output square j (stores
+// coalesced along j; the loads are a permutation of one 225-element row).
+__global__ __launch_bounds__(256) void replay_gather_kernel(
+    const int8_t* __restrict__ stones, const float* __restrict__ pis, const float* __restrict__ zs, int cap_pos,
+    int head, int count, int nsym, const int64_t* __restrict__ ids, float* __restrict__ x,
+    float* __restrict__ pi_out, float* __restrict__ z_out)
+{
+    const int b = blockIdx.x;
+    // an id outside [0, count * nsym) is clamped: it never reads outside the ring
+    const int64_t last = (int64_t)count * nsym - 1;
+    int64_t id = ids[b];
+    id = id < 0 ? 0 : (id > last ? last : id);
+    const int s = (int)(id % nsym);
+    const int pos = (int)(((int64_t)head + id / nsym) % cap_pos);
+    const int j = threadIdx.x;
+    if (j < PIX) {
+        const int y = j / BOARD, xx = j - y * BOARD;
+        const int src = replay_src(y, xx, s);
+        const int8_t v = stones[(size_t)pos * PIX + src];
+        float* xo = x + (size_t)b * 3 * PIX;
+        xo[j] = v == 1 ? 1.f : 0.f;
+        xo[PIX + j] = v == 2 ? 1.f : 0.f;
+        xo[2 * PIX + j] = 1.f;
+        pi_out[(size_t)b * PIX + j] = pis[(size_t)pos * PIX + src];
+    }
+    if (j == 0) z_out[b] = zs[pos];
+}
+
+}  // namespace azg
+
+extern "C" int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, const float* zs, int32_t cap_pos,
+                                        int32_t head, int32_t count, int32_t nsym, const int64_t* ids, int32_t batch,
+                                        float* x, float* pi_out, float* z_out, void* stream)
+{
+    using namespace azg;
+    if (!stones || !pis || !zs || !ids || !x || !pi_out || !z_out)
+        return set_error("azg_pv_replay_gather: null argument", hipSuccess);
+    if (nsym != 1 && nsym != 8) return set_error("azg_pv_replay_gather: nsym must be 1 or 8", hipSuccess);
+    if (batch < 1) return set_error("azg_pv_replay_gather: batch must be >= 1", hipSuccess);
+    if (cap_pos < 1) return set_error("azg_pv_replay_gather: cap_pos must be >= 1", hipSuccess);
+    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_gather: count outside [1, cap_pos]", hipSuccess);
+    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_gather: head outside [0, cap_pos)", hipSuccess);
+    hipLaunchKernelGGL(replay_gather_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, stones, pis, zs,
+                       cap_pos, head, count, nsym, ids, x, pi_out, z_out);
+    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_gather: launch", e);
+    return 0;
+}

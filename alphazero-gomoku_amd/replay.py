@@ -1,0 +1,207 @@
+"""Device-resident replay buffer with on-GPU symmetry sampling.
+
+``DeviceReplayBuffer`` is a drop-in for selfplay.ReplayBuffer (reference
+train.py:272-297) whose storage lives on the GPU.  The host buffer keeps every
+position eight times (its dihedral images, 3,604 B of fp32 each) in a deque of
+tuples and forms a batch with random.sample + np.stack + three pageable copies.
+This one keeps every position ONCE, compactly -- int8 stones (0 empty, 1 side to
+move, 2 opponent: plane 2 of the encoding is constant ones), fp32 pi, fp32 z =
+1,129 B -- in a preallocated ring, and a HIP kernel (csrc/pv_replay.hip,
+azg_pv_replay_gather) forms the batch: the reference's encoding
+(games/gomoku.py:130-150) and the image's rotation / flip (MCTS.symmetries,
+mcts/new_mcts_alpha.py) on the fly.
+
+Image numbering makes the two buffers interchangeable: image i of this buffer is
+element i of the host deque (position i // 8 in ring order, symmetry i % 8), and
+random.sample picks by index from (len, k) alone, so under the same random.seed
+``sample`` returns the host buffer's batch bit for bit.
+"""
+from __future__ import annotations
+
+import random
+from typing import Optional
+
+import numpy as np
+import torch
+
+from _native import check, load_library, ptr
+from selfplay import ReplayBuffer
+
+_N = 15
+_PIX = _N * _N
+
+
+def _images(S: np.ndarray, P: np.ndarray):
+    """The 8 dihedral images of S [T,C,n,n] / P [T,n,n] in MCTS.symmetries' order
+    (rotation k, then its column flip), formed for all T at once as
+    NativeSelfPlay._finish does."""
+    T = len(S)
+    out = []
+    for k in range(4):
+        s_k = np.rot90(S, k, axes=(2, 3))
+        p_k = np.rot90(P, k, axes=(1, 2))
+        out.append((np.ascontiguousarray(s_k), np.ascontiguousarray(p_k).reshape(T, -1)))
+        out.append((np.ascontiguousarray(np.flip(s_k, axis=3)),
+                    np.ascontiguousarray(np.flip(p_k, axis=2)).reshape(T, -1)))
+    return out
+
+
+def _stack(examples):
+    S = np.stack([np.asarray(e[0]) for e in examples]).astype(np.float32, copy=False)
+    P = np.stack([np.asarray(e[1]) for e in examples]).astype(np.float32, copy=False)
+    Z = np.array([e[2] for e in examples], dtype=np.float32)
+    if S.shape[1:] != (3, _N, _N) or P.shape[1:] != (_PIX,):
+        raise ValueError(f"examples must be (state [3,{_N},{_N}], pi [{_PIX}], z), got {S.shape[1:]} / {P.shape[1:]}")
+    return S, P, Z
+
+
+class DeviceReplayBuffer:
+    """``capacity`` counts images like the reference's deque(maxlen=capacity); the ring
+    holds capacity // nsym positions, nsym = 8 if ``symmetries`` else 1."""
+
+    def __init__(self, capacity: int, device, symmetries: bool = True, board_size: int = 15):
+        self.nsym = 8 if symmetries else 1
+        if board_size != _N:
+            raise ValueError("the replay gather is built for 15x15 boards only")
+        if capacity < self.nsym or capacity % self.nsym != 0:
+            raise ValueError(f"capacity ({capacity}) must be a positive multiple of {self.nsym}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceReplayBuffer needs a HIP (MI355X) device; the host buffer is selfplay.ReplayBuffer")
+        self.lib = load_library()
+        self.capacity = capacity
+        self.cap_pos = capacity // self.nsym
+        self.stones = torch.zeros((self.cap_pos, _PIX), dtype=torch.int8, device=self.device)
+        self.pis = torch.zeros((self.cap_pos, _PIX), dtype=torch.float32, device=self.device)
+        self.zs = torch.zeros(self.cap_pos, dtype=torch.float32, device=self.device)
+        self.head = 0     # slot of the oldest position
+        self.count = 0    # positions held
+
+    def __len__(self) -> int:
+        return self.count * self.nsym
+
+    # ---------------------------------------------------------------- writing
+    def add_positions(self, examples) -> None:
+        """Canonical (state [3,15,15], pi [225], z) tuples, as
+        selfplay_games(use_symmetries=False) returns them; the oldest positions are
+        overwritten (= the deque's eviction of whole groups of nsym images)."""
+        examples = list(examples)
+        if not examples:
+            return
+        S, P, Z = _stack(examples)
+        p0, p1 = S[:, 0], S[:, 1]
+        if not (((p0 == 0) | (p0 == 1)).all() and ((p1 == 0) | (p1 == 1)).all()):
+            raise ValueError("state planes 0 / 1 must hold 0 or 1")
+        if (p0 * p1).any():
+            raise ValueError("state planes 0 and 1 must be disjoint")
+        if not (S[:, 2] == 1).all():
+            raise ValueError("state plane 2 must be all ones (games/gomoku.py:146-150)")
+        stones = (p0 + 2 * p1).astype(np.int8).reshape(len(S), _PIX)
+        if len(S) > self.cap_pos:     # only the newest cap_pos survive, as in the deque
+            stones, P, Z = stones[-self.cap_pos:], P[-self.cap_pos:], Z[-self.cap_pos:]
+        n = len(stones)
+        # one pinned staging buffer [pis | zs | stones]; torch's host allocator keeps the
+        # block alive until the copies queued from it have run
+        stage = torch.empty(n * (_PIX * 4 + 4 + _PIX), dtype=torch.uint8, pin_memory=True)
+        o1, o2 = n * _PIX * 4, n * _PIX * 4 + n * 4
+        h_pi = stage[:o1].view(torch.float32).view(n, _PIX)
+        h_z = stage[o1:o2].view(torch.float32)
+        h_st = stage[o2:].view(torch.int8).view(n, _PIX)
+        h_pi.numpy()[...] = P
+        h_z.numpy()[...] = Z
+        h_st.numpy()[...] = stones
+        tail = (self.head + self.count) % self.cap_pos
+        first = min(n, self.cap_pos - tail)
+        for lo, hi, at in ((0, first, tail), (first, n, 0)):   # the write splits in two when it wraps
+            if hi > lo:
+                self.pis[at:at + hi - lo].copy_(h_pi[lo:hi], non_blocking=True)
+                self.zs[at:at + hi - lo].copy_(h_z[lo:hi], non_blocking=True)
+                self.stones[at:at + hi - lo].copy_(h_st[lo:hi], non_blocking=True)
+        over = self.count + n - self.cap_pos
+        if over > 0:
+            self.head = (self.head + over) % self.cap_pos
+        self.count = min(self.count + n, self.cap_pos)
+
+    # --------------------------------------------------------------- sampling
+    def draw_ids(self, batch_size: int) -> list:
+        """The indices a seeded random.sample(deque, batch_size) picks on the host buffer."""
+        return random.sample(range(len(self)), batch_size)
+
+    def sample(self, batch_size: int, ids=None):
+        """Device tensors (s [B,3,15,15], p [B,225], z [B,1]); no host sync."""
+        ids = np.asarray(self.draw_ids(batch_size) if ids is None else ids, dtype=np.int64).reshape(-1)
+        if len(ids) != batch_size or batch_size < 1:
+            raise ValueError(f"{len(ids)} ids for a batch of {batch_size}")
+        if int(ids.min()) < 0 or int(ids.max()) >= len(self):
+            raise ValueError(f"image id outside [0, {len(self)})")
+        dev = self.device
+        h_ids = torch.empty(batch_size, dtype=torch.int64, pin_memory=True)
+        h_ids.numpy()[...] = ids
+        with torch.cuda.device(dev):
+            d_ids = h_ids.to(dev, non_blocking=True)
+            s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
+            p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
+            z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
+            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(self.pis), ptr(self.zs), self.cap_pos,
+                                                self.head, self.count, self.nsym, ptr(d_ids), batch_size,
+                                                ptr(s), ptr(p), ptr(z),
+                                                torch.cuda.current_stream(dev).cuda_stream), self.lib)
+        return s, p, z
+
+    # ------------------------------------------------------------ host format
+    def to_host(self) -> ReplayBuffer:
+        """A ReplayBuffer whose deque holds the reference-format examples in deque order
+        (nsym = 8: each position's 8 images in MCTS.symmetries' order), so
+        save_replay_buffer keeps writing the reference pickle."""
+        out = ReplayBuffer(capacity=self.capacity)
+        if not self.count:
+            return out
+        order = (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
+        st = self.stones[order].cpu().numpy().reshape(self.count, _N, _N)
+        P = self.pis[order].cpu().numpy()
+        zs = [float(v) for v in self.zs[order].cpu().numpy()]
+        S = np.empty((self.count, 3, _N, _N), dtype=np.float32)
+        S[:, 0] = st == 1
+        S[:, 1] = st == 2
+        S[:, 2] = 1.0
+        if self.nsym == 1:
+            out.add([(S[t], P[t], zs[t]) for t in range(self.count)])
+        else:
+            imgs = _images(S, P.reshape(self.count, _N, _N))
+            out.add([(si[t], pi[t], zs[t]) for t in range(self.count) for si, pi in imgs])
+        return out
+
+    @classmethod
+    def from_host(cls, buffer: ReplayBuffer, device) -> "DeviceReplayBuffer":
+        """nsym = 8 from every eighth example when the host buffer is whole groups of 8
+        dihedral images (capacity and length multiples of 8, every aligned group the
+        images of its first element with one z); otherwise nsym = 1 with each example
+        as its own entry."""
+        examples = list(buffer.buffer)
+        grouped = buffer.capacity % 8 == 0 and len(examples) % 8 == 0
+        if grouped and examples:
+            try:
+                S, P, Z = _stack(examples)
+            except ValueError:
+                grouped = False
+            else:
+                G = len(S) // 8
+                S8, P8, Z8 = S.reshape(G, 8, 3, _N, _N), P.reshape(G, 8, _PIX), Z.reshape(G, 8)
+                grouped = bool((Z8 == Z8[:, :1]).all())
+                if grouped:
+                    for s, (si, pi) in enumerate(_images(S8[:, 0], P8[:, 0].reshape(G, _N, _N))):
+                        if not (np.array_equal(si, S8[:, s]) and np.array_equal(pi, P8[:, s])):
+                            grouped = False
+                            break
+        out = cls(buffer.capacity, device, symmetries=grouped)
+        out.add_positions(examples[::8] if grouped else examples)
+        return out
+
+
+def new_device_buffer(loaded: Optional[ReplayBuffer], capacity: int, device) -> DeviceReplayBuffer:
+    """The loop's buffer: a loaded host buffer moved to the device, or an empty one
+    (nsym = 8 unless ``capacity`` is no multiple of 8, where only single images
+    reproduce the deque's eviction)."""
+    if loaded is not None:
+        return DeviceReplayBuffer.from_host(loaded, device)
+    return DeviceReplayBuffer(capacity, device, symmetries=capacity % 8 == 0)

@@ -146,10 +146,15 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     next_iteration_continuation: int = 1, dirichlet_alpha: float = 0.03,
                     dirichlet_epsilon: float = 0.25, dirichlet_n_moves: int = 30, n_res_blocks: int = 3,
                     channels: int = 64, device: Optional[str] = None, max_moves: Optional[int] = None,
-                    **reference_worker_kwargs):
+                    device_buffer: bool = False, **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
-    ignored: concurrency comes from batching games on the GPU."""
+    ignored: concurrency comes from batching games on the GPU.
+
+    device_buffer=True keeps the replay buffer on the GPU (replay.DeviceReplayBuffer):
+    self-play hands over canonical positions only, every batch is gathered (encoding +
+    dihedral image) by a HIP kernel, and the step reads it in place.  Same batches, same
+    model and same buffer pickle as the default host deque under the same seeds."""
     r, w, _, dev = D.init_from_env()
     device = device or str(dev)
     main = r == 0
@@ -169,7 +174,14 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
 
     suffix = "" if r == 0 else f"_rank{r}"
     buffer_path = os.path.join(model_dir, f"replay_buffer_latest{suffix}.pkl")
-    buffer = load_replay_buffer(buffer_path, capacity=buffer_size) or ReplayBuffer(capacity=buffer_size)
+    if device_buffer:
+        from replay import new_device_buffer
+        buffer = new_device_buffer(load_replay_buffer(buffer_path, capacity=buffer_size), buffer_size, device)
+    else:
+        buffer = load_replay_buffer(buffer_path, capacity=buffer_size) or ReplayBuffer(capacity=buffer_size)
+    # a device buffer of single images (nsym = 1: a loaded buffer that is not whole groups
+    # of 8) takes the expanded examples like the deque; otherwise it forms the images itself
+    host_symmetries = not device_buffer or buffer.nsym == 1
     temp_fn = lambda n: max(0.0, 1.0 - n / temp_threshold)
     max_moves = max_moves or board_size * board_size
     last = next_iteration_continuation + num_iterations - 1
@@ -181,8 +193,12 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         n_local = len(D.shard(games_per_iteration))
         examples, winners, drv = selfplay_games(model_candidate, GameClass, n_local, n_simulations, cpuct, temp_fn,
                                                 dirichlet_alpha, dirichlet_epsilon, dirichlet_n_moves,
-                                                max_moves=max_moves, board_size=board_size)
-        buffer.add(examples)
+                                                max_moves=max_moves, board_size=board_size,
+                                                use_symmetries=host_symmetries)
+        if device_buffer:
+            buffer.add_positions(examples)
+        else:
+            buffer.add(examples)
         t_sp = time.time() - t0
         if main:
             print(f"self-play done: {t_sp / 60:.2f} min, winners={winners}, buffer={len(buffer)}, "
@@ -196,7 +212,10 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                 te = time.time()
                 for _ in range(n_batches):
                     s, p, z = buffer.sample(batch_size)
-                    loss_info = model_candidate.train_batch(s, p, z, epochs=1)
+                    if device_buffer:   # the synchronous step: a skipped step is redone as on the host path
+                        loss_info = model_candidate.train_batch_device(s, p, z, epochs=1)
+                    else:
+                        loss_info = model_candidate.train_batch(s, p, z, epochs=1)
                 if main:
                     print(f"  epoch {epoch + 1}/{epochs_per_iter} {time.time() - te:.1f}s last_loss={loss_info}")
             D.sync_bn_stats(model_candidate)
@@ -230,7 +249,7 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             path = os.path.join(model_dir, f"snapshot_iter{it}_{datetime.now():%Y%m%d_%H%M%S}.pt")
             model_best.save(path)
             print(f" saved snapshot: {path}")
-        save_replay_buffer(buffer, buffer_path)
+        save_replay_buffer(buffer.to_host() if device_buffer else buffer, buffer_path)
         if main:
             print(f"iteration {it} done in {(time.time() - t0) / 60:.2f} min; winners {winners}")
     if main:

@@ -134,6 +134,27 @@ int32_t azg_pv_train_apply(azg_pv* h, float* exp_avg, float* exp_avg_sq,
  * MFMA (tuning key 49 = 0 for that one step): the redo of a skipped step. */
 int32_t azg_pv_train_fp32_once(azg_pv* h);
 
+/* Training batch from a device-resident replay ring (handle-free; replaces
+ * ReplayBuffer.sample's random.sample + np.stack + three host-to-device copies, reference
+ * train.py:272-297, and the 8 stored images per position of MCTS.symmetries,
+ * mcts/new_mcts_alpha.py:42-56).  The ring stores each position ONCE: stones
+ * [cap_pos][225] int8 (0 empty, 1 side to move, 2 opponent), pis [cap_pos][225], zs
+ * [cap_pos]; it holds `count` positions, the oldest at slot `head`.  nsym is 1 or 8.
+ * ids [batch] (device, int64) are image numbers in [0, count*nsym): image i is symmetry
+ * i % nsym of position (head + i / nsym) % cap_pos; symmetry s is np.rot90 by k = s / 2
+ * (counter-clockwise) followed by a column flip when s is odd.  An id outside the range
+ * is clamped into it (the kernel never reads outside the ring; callers range-check on
+ * the host).  Outputs: x [batch,3,15,15] (planes stones == 1, stones == 2, ones:
+ * games/gomoku.py:130-150), pi_out [batch,225], z_out [batch,1] -- copies and 0/1
+ * constants only, so bitwise what numpy gives.  Arguments are checked before any device
+ * call: a null pointer, nsym not 1 or 8, batch < 1, cap_pos < 1, count outside
+ * [1, cap_pos] or head outside [0, cap_pos) return nonzero.  One launch, asynchronous
+ * on `stream`, no allocation. */
+int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, const float* zs,
+                             int32_t cap_pos, int32_t head, int32_t count, int32_t nsym,
+                             const int64_t* ids, int32_t batch,
+                             float* x, float* pi_out, float* z_out, void* stream);
+
 /* Kernel-class event timing (bench / roofline instrumentation).  When enabled,
  * every launch of a profiled class is bracketed by hipEvents on the stream it is
  * launched on; azg_pv_profile_read synchronises those events and returns the
