@@ -62,6 +62,27 @@ int main()
         CHECK(azg_pv_forward(h, &dummy, 1, &dummy, &dummy, nullptr, nullptr) != 0);
         CHECK(std::strlen(azg_pv_last_error()) > 0);
         CHECK(azg_pv_forward_boards(h, nullptr, nullptr, 1, &dummy, &dummy, nullptr, nullptr) != 0);
+        {   // the symmetric board forward: argument errors first, then "not bound"
+            int8_t i8 = 0;
+            const auto names_it = [] { return std::strstr(azg_pv_last_error(), "azg_pv_forward_boards_sym") != nullptr; };
+            CHECK(azg_pv_forward_boards_sym(nullptr, &i8, &i8, &i8, 0, 1, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, 2, 1, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, -1, 1, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(std::strstr(azg_pv_last_error(), "mode") != nullptr);
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, nullptr, 1, 2049, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(std::strstr(azg_pv_last_error(), "2048") != nullptr);
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, 0, -1, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(azg_pv_forward_boards_sym(h, nullptr, &i8, &i8, 0, 1, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(azg_pv_forward_boards_sym(h, &i8, nullptr, &i8, 0, 1, &dummy, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, 0, 1, nullptr, &dummy, &dummy, nullptr) != 0 && names_it());
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, 1, 1, &dummy, nullptr, &dummy, nullptr) != 0 && names_it());
+            CHECK(std::strstr(azg_pv_last_error(), "null") != nullptr);
+            // valid arguments (syms and priors are optional) on the unbound handle
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, nullptr, 0, 1, &dummy, &dummy, nullptr, nullptr) != 0 && names_it());
+            CHECK(std::strstr(azg_pv_last_error(), "not bound") != nullptr);
+            CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, 1, 2048, &dummy, &dummy, &dummy, nullptr) != 0);
+            CHECK(std::strstr(azg_pv_last_error(), "not bound") != nullptr);
+        }
         CHECK(azg_pv_train_backward(h, &dummy, &dummy, &dummy, 4, &dummy, nullptr) != 0);
         CHECK(azg_pv_train_apply(h, &dummy, &dummy, 1, 1e-3f, 0.9f, 0.999f, 1e-8f, 1e-4f, 3.f, nullptr, nullptr) != 0);
         CHECK(azg_pv_destroy(h) == 0);

@@ -217,6 +217,34 @@ int32_t azg_pv_forward_boards(azg_pv* h, const int8_t* boards, const int8_t* pla
     return forward_eval(h, nullptr, batch, probs, values, nullptr, st, boards, players, priors);
 }
 
+int32_t azg_pv_forward_boards_sym(azg_pv* h, const int8_t* boards, const int8_t* players, const int8_t* syms,
+                                  int32_t mode, int32_t batch, float* probs, float* values, float* priors,
+                                  void* stream)
+{
+    // argument checks first: before the bound check and before any device call
+    if (!h) return fail("azg_pv_forward_boards_sym: null handle");
+    if (mode != 0 && mode != 1) return fail("azg_pv_forward_boards_sym: mode must be 0 (per-board syms) or 1 (mean of 8)");
+    if (batch < 0) return fail("azg_pv_forward_boards_sym: negative batch");
+    if (mode == 1 && batch > 2048)
+        return fail("azg_pv_forward_boards_sym: mode 1 takes at most 2048 boards per call (8 images each)");
+    if (batch > 0 && (!boards || !players || !probs || !values))
+        return fail("azg_pv_forward_boards_sym: null boards/players/probs/values");
+    if (!h->params) return fail("azg_pv_forward_boards_sym: handle not bound (azg_pv_bind)");
+    if (h->cfg.board != BOARD || h->cfg.in_ch != 3)
+        return fail("azg_pv_forward_boards_sym: needs a 15x15, 3-plane net");
+    if (batch == 0) return 0;
+    const int symmode = mode == 1 ? SYM_MEAN8 : syms ? SYM_EACH : SYM_NONE;   // no syms: the plain forward
+    const int images = symmode == SYM_MEAN8 ? 8 * batch : batch;
+    hipStream_t st = (hipStream_t)stream;
+    if (int32_t r = ensure_eval_workspace(h, images, st)) return r;
+    if (h->dirty) {
+        if (int32_t r = repack(h, st)) return r;
+        h->dirty = false;
+    }
+    return forward_eval(h, nullptr, batch, probs, values, nullptr, st, boards, players, priors, false, false, 0u,
+                        symmode == SYM_EACH ? syms : nullptr, symmode);
+}
+
 int32_t azg_pv_profile_enable(azg_pv* h, int32_t enable)
 {
     if (!h) return fail("azg_pv_profile_enable: null handle");
@@ -330,7 +358,7 @@ int32_t azg_pv_recover(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream
     hipStream_t rst = (hipStream_t)stream;
     const bool guard = !ovf && r.h3;
     if (int32_t e = forward_eval(h, r.x, r.batch, r.probs, r.values, r.logits, rst, r.boards, r.players, r.priors,
-                                 true, ovf, guard ? seq : 0u))
+                                 true, ovf, guard ? seq : 0u, r.syms, r.symmode))
         return e;
     bool late_ovf = false;
     if (guard) {
@@ -339,7 +367,7 @@ int32_t azg_pv_recover(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream
         if (late_ovf) {
             __atomic_store_n(h->ovf_host + slot, 0u, __ATOMIC_RELEASE);
             if (int32_t e = forward_eval(h, r.x, r.batch, r.probs, r.values, r.logits, rst, r.boards, r.players,
-                                         r.priors, true, true))
+                                         r.priors, true, true, 0u, r.syms, r.symmode))
                 return e;
         }
     }
@@ -638,14 +666,16 @@ static int conv_tuned_shape_h3(azg_pv* h, int batch, hipStream_t, const float*, 
 
 static int32_t stem_and_tower(azg_pv* h, int variant, const float* x, int batch, hipStream_t st,
                               const int8_t* boards, const int8_t* players, float** out, unsigned seq = 0,
-                              bool h3 = false, bool recompute = false)
+                              bool h3 = false, bool recompute = false, const int8_t* syms = nullptr,
+                              int symmode = SYM_NONE)
 {
+    // symmode != SYM_NONE: batch counts images (the stem reads them through the symmetries)
     const int C = h->C;
     const int M = batch * PIX;
     const BnDesc* bd = h->bn_desc.data();
     int pr = prof_begin(h, AZG_PROF_STEM, st, batch);
     AZG_TRY(launch_stem(C, EPI_BN_RELU, x, h->wstem, h->scale + bd[h->bn_stem].out_off,
-                        h->shift + bd[h->bn_stem].out_off, h->act[0], batch, st, boards, players),
+                        h->shift + bd[h->bn_stem].out_off, h->act[0], batch, st, boards, players, syms, symmode),
             "forward: stem");
     prof_end(h, pr, st);
     float* X = h->act[0];
@@ -792,7 +822,7 @@ static int32_t stem_and_tower(azg_pv* h, int variant, const float* x, int batch,
 // and is not a candidate; key 6 = 10 forces it.  While the stream is being captured
 // the untuned default is used.  All variants are bitwise identical.
 static int tower_variant(azg_pv* h, const float* x, int batch, hipStream_t st, const int8_t* boards,
-                         const int8_t* players, bool h3)
+                         const int8_t* players, bool h3, const int8_t* syms = nullptr, int symmode = SYM_NONE)
 {
     if (h->NB == 0 || h->NB > kTowerMaxBlocks) return 0;
     if ((size_t)batch * PADPIX * h->C * sizeof(float) >= (size_t)INT32_MAX) return 0;
@@ -828,7 +858,8 @@ static int tower_variant(azg_pv* h, const float* x, int batch, hipStream_t st, c
             for (int r = 0; r < 3 && ok; ++r)
                 for (int c = 0; c < ncand && ok; ++c) {
                     ok = hipEventRecord(e0, st) == hipSuccess &&
-                         stem_and_tower(h, cand[c], x, batch, st, boards, players, &out, 0, h3) == 0 &&
+                         stem_and_tower(h, cand[c], x, batch, st, boards, players, &out, 0, h3, false, syms,
+                                        symmode) == 0 &&
                          hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
                     float ms = 0.f;
                     if (ok && r > 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < best_ms[c]) best_ms[c] = ms;
@@ -858,8 +889,11 @@ static int tower_variant(azg_pv* h, const float* x, int batch, hipStream_t st, c
 
 int32_t forward_eval(azg_pv* h, const float* x, int batch, float* probs, float* values, float* logits,
                      hipStream_t st, const int8_t* boards, const int8_t* players, float* priors, bool per_layer,
-                     bool fp32_only, unsigned guard_seq)
+                     bool fp32_only, unsigned guard_seq, const int8_t* syms, int symmode)
 {
+    // `batch` boards; under SYM_MEAN8 the stem, the tower and the heads' fc see 8 images each
+    const int boards_n = batch;
+    if (symmode == SYM_MEAN8) batch *= 8;
     const int C = h->C;
     const float* P = h->params;
     const BnDesc* bd = h->bn_desc.data();
@@ -871,7 +905,7 @@ int32_t forward_eval(azg_pv* h, const float* x, int batch, float* probs, float* 
     // key 19 = 2 at C = 128: the 16x16x32 board tower is the one form of its arithmetic, for
     // every batch and path (it has no cross-workgroup waits: nothing for the breaker to avoid)
     const bool k32 = h3 && g_tower_h3 == 2 && C == 128 && h->NB <= kTowerMaxBlocks;
-    int variant = k32 ? 14 : per_layer ? 0 : tower_variant(h, x, batch, st, boards, players, h3);
+    int variant = k32 ? 14 : per_layer ? 0 : tower_variant(h, x, batch, st, boards, players, h3, syms, symmode);
     if (variant != 0 && !k32 && h->breaker_until > 0.0) {
         if (now_s() < h->breaker_until) {
             variant = 0;
@@ -887,20 +921,21 @@ int32_t forward_eval(azg_pv* h, const float* x, int batch, float* probs, float* 
         seq = ++h->seq;
         if (seq == 0) seq = ++h->seq;   // 0 means "not posted"
         azg_pv::LaunchRec& r = h->launches[seq & (kTowerRing - 1)];
-        r = azg_pv::LaunchRec{seq, x, boards, players, batch, h3, probs, values, logits, priors};
+        r = azg_pv::LaunchRec{seq, x, boards, players, boards_n, h3, probs, values, logits, priors, syms, symmode};
         __atomic_store_n(h->ring_host + (seq & (kTowerRing - 1)), 0u, __ATOMIC_RELEASE);
         __atomic_store_n(h->ovf_host + (seq & (kTowerRing - 1)), 0u, __ATOMIC_RELEASE);
     }
     if (!per_layer) h->last_seq = seq;
     float* X = nullptr;
     h->b16_split = false;
-    if (int32_t r = stem_and_tower(h, variant, x, batch, st, boards, players, &X, seq, h3, per_layer)) return r;
+    if (int32_t r = stem_and_tower(h, variant, x, batch, st, boards, players, &X, seq, h3, per_layer, syms, symmode))
+        return r;
     const int ho = bd[h->bn_pol].out_off;   // policy (2) then value (1): contiguous
     int pr = prof_begin(h, AZG_PROF_HEADS, st, batch);
     AZG_TRY(launch_heads_fwd(C, X, P + h->poff[h->t_pc_w], P + h->poff[h->t_vc_w], h->scale + ho, h->shift + ho,
                              h->wfc, P + h->poff[h->t_pfc_b], P + h->poff[h->t_vfc1_b],
                              P + h->poff[h->t_vfc2_w], P + h->poff[h->t_vfc2_b], h->hbuf, probs, values, logits,
-                             batch, st, boards, priors, variant == 14 && !h->b16_split),
+                             batch, st, boards, priors, variant == 14 && !h->b16_split, syms, symmode),
             "forward: heads");
     prof_end(h, pr, st);
     return 0;

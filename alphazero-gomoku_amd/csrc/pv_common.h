@@ -41,6 +41,30 @@ __device__ __forceinline__ int pad_off(int m, int C) {
     return (b * PADPIX + (y + 1) * PADW + (x + 1)) * C;
 }
 
+// Board symmetry s in 0..7 (MCTS.symmetries, mcts/new_mcts_alpha.py:42-56): np.rot90 by
+// k = s >> 1 (counter-clockwise), then a column flip when s is odd.  Source square of image
+// square (y, x): image[y][x] = board[sym_src(y, x, s)].  With r = np.rot90(a, k),
+// r[y][x] = a[x][n-1-y] for k = 1 (and its powers); np.flip(r, columns)[y][x] = r[y][n-1-x].
+// Shared by the replay gather (pv_replay.hip) and the symmetric leaf evaluation (the
+// board-input stems of pv_conv.hip read through it, pv_heads.hip stores through it).
+__host__ __device__ __forceinline__ int sym_src(int y, int x, int s)
+{
+    constexpr int n = BOARD;
+    if (s & 1) x = n - 1 - x;
+    switch (s >> 1) {
+    case 0: return y * n + x;
+    case 1: return x * n + (n - 1 - y);
+    case 2: return (n - 1 - y) * n + (n - 1 - x);
+    default: return (n - 1 - x) * n + y;
+    }
+}
+// how a board-input forward applies symmetries (azg_pv_forward_boards_sym)
+enum SymMode : int {
+    SYM_NONE = 0,   // image i = board i as stored
+    SYM_EACH = 1,   // image i = board i under syms[i] & 7; outputs back in the board's coordinates
+    SYM_MEAN8 = 2,  // image i = board i / 8 under i % 8; outputs: the mean of a board's 8 images
+};
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

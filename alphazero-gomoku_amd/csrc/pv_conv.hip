@@ -256,24 +256,29 @@ __global__ __launch_bounds__(64 * NWT) __attribute__((amdgpu_waves_per_eu(4))) v
 // [B]; the reference encoding (games/gomoku.py:130-150: planes board==player,
 // board==opponent, ones) is built straight into the LDS patch (on-GPU encode, no
 // float planes in HBM).
-template <int C, int EPI, bool BOARDS = false>
+// SYM (BOARDS only, pv_common.h SymMode): workgroup b builds image b -- board b read through
+// symmetry syms[b] & 7 (SYM_EACH), or board b / 8 through symmetry b % 8 (SYM_MEAN8).
+template <int C, int EPI, bool BOARDS = false, int SYM = SYM_NONE>
 __global__ __launch_bounds__(256) void stem_conv(
     const float* __restrict__ x, const int8_t* __restrict__ boards, const int8_t* __restrict__ players,
     const float* __restrict__ ws, const float* __restrict__ scale, const float* __restrict__ shift,
-    float* __restrict__ out)
+    float* __restrict__ out, const int8_t* __restrict__ syms = nullptr)
 {
+    static_assert(SYM == SYM_NONE || BOARDS, "symmetries are applied to board inputs only");
     __shared__ float xs[3 * PADPIX];
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
     const float* xb = x + (size_t)b * 3 * PIX;
-    const int8_t* bb = boards + (size_t)b * PIX;
-    const int me = BOARDS ? (int)players[b] : 0;
+    const int bsrc = SYM == SYM_MEAN8 ? b >> 3 : b;                       // the board of image b
+    const int sym = SYM == SYM_MEAN8 ? b & 7 : SYM == SYM_EACH ? (int)syms[b] & 7 : 0;
+    const int8_t* bb = boards + (size_t)bsrc * PIX;
+    const int me = BOARDS ? (int)players[bsrc] : 0;
     for (int i = tid; i < 3 * PADPIX; i += 256) {
         const int ci = i / PADPIX, rem = i - ci * PADPIX;
         const int yy = rem / PADW, xx = rem - yy * PADW;
         float v = 0.f;
         if (yy >= 1 && yy <= BOARD && xx >= 1 && xx <= BOARD) {
-            const int p = (yy - 1) * BOARD + (xx - 1);
+            const int p = SYM != SYM_NONE ? sym_src(yy - 1, xx - 1, sym) : (yy - 1) * BOARD + (xx - 1);
             if (BOARDS) {
                 const int c = bb[p];
                 v = ci == 0 ? (c == me ? 1.f : 0.f) : ci == 1 ? (c == 3 - me ? 1.f : 0.f) : 1.f;
@@ -333,13 +338,19 @@ constexpr int STEM_CW = 64;   // channels per wave (2 accumulators): twice the w
 // the mean and M2 of the raw stem output straight from the accumulators (two-pass, fp32)
 // -> pa / pb [tile][C], combined exactly in fp64 by bn_fin_tiles_kernel (prow 128): the
 // col_stats pass over z0 disappears.  Waves past M stay (barriers) but store nothing.
-template <int C, int EPI, bool BOARDS, int ABL = 0, bool STATS = false>
+// SYM (BOARDS only, pv_common.h SymMode): pixel (y, x) of image i reads its neighbourhood
+// cells as boards[board_of(i)][sym_src(yy, xx, s_i)] -- board_of(i) = i, s_i = syms[i] & 7
+// (SYM_EACH) or board_of(i) = i / 8, s_i = i % 8 (SYM_MEAN8).  Off-board handling and the
+// arithmetic are the BOARDS path's; a template flag, so SYM_NONE compiles to what it was.
+template <int C, int EPI, bool BOARDS, int ABL = 0, bool STATS = false, int SYM = SYM_NONE>
 __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, const int8_t* __restrict__ boards,
                                                  const int8_t* __restrict__ players, const float* __restrict__ ws,
                                                  const float* __restrict__ scale, const float* __restrict__ shift,
                                                  float* __restrict__ out, int M, float* __restrict__ pa = nullptr,
-                                                 float* __restrict__ pb = nullptr)
+                                                 float* __restrict__ pb = nullptr,
+                                                 const int8_t* __restrict__ syms = nullptr)
 {
+    static_assert(SYM == SYM_NONE || BOARDS, "symmetries are applied to board inputs only");
     constexpr int CW = C < STEM_CW ? C : STEM_CW;
     constexpr int NJ = CW / 32;
     constexpr int KS = 14;                       // MFMA steps (K = 27 padded to 28)
@@ -365,13 +376,15 @@ __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, co
     // the 9 neighbourhood values of each input plane (0 outside the board)
     float nb[3][9];
     if (BOARDS) {
-        const int8_t* bb = boards + (size_t)b * PIX;
-        const int me = (int)players[b];
+        const int bsrc = SYM == SYM_MEAN8 ? b >> 3 : b;                   // the board of image b
+        const int sym = SYM == SYM_MEAN8 ? b & 7 : SYM == SYM_EACH ? (int)syms[b] & 7 : 0;
+        const int8_t* bb = boards + (size_t)bsrc * PIX;
+        const int me = (int)players[bsrc];
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int yy = y + t / 3 - 1, xx = xq + t % 3 - 1;
             const bool in = yy >= 0 && yy < BOARD && xx >= 0 && xx < BOARD;
-            const int c = in ? (int)bb[yy * BOARD + xx] : -1;
+            const int c = in ? (int)bb[SYM != SYM_NONE ? sym_src(yy, xx, sym) : yy * BOARD + xx] : -1;
             nb[0][t] = c == me ? 1.f : 0.f;
             nb[1][t] = c == 3 - me ? 1.f : 0.f;
             nb[2][t] = in ? 1.f : 0.f;
@@ -978,10 +991,33 @@ int g_stem_ablation = 0;  // timing studies only (C = 128 float-plane stem)
 
 hipError_t launch_stem(int C, int epi, const float* x, const float* ws, const float* scale,
                        const float* shift, float* out, int B, hipStream_t st, const int8_t* boards,
-                       const int8_t* players)
+                       const int8_t* players, const int8_t* syms, int symmode)
 {
     if (B <= 0) return hipSuccess;
     if (epi != EPI_RAW && epi != EPI_BN_RELU) return hipErrorInvalidValue;
+    if (symmode != SYM_NONE) {
+        // B images of the caller's boards (SYM_EACH: syms [B]; SYM_MEAN8: B = 8 x boards)
+        if (!boards || epi != EPI_BN_RELU || (symmode != SYM_EACH && symmode != SYM_MEAN8) ||
+            (symmode == SYM_EACH && !syms) || (symmode == SYM_MEAN8 && B % 8 != 0))
+            return hipErrorInvalidValue;
+        const int M = B * PIX;
+        const int cw = C < STEM_CW ? C : STEM_CW;
+        const dim3 grid((M + 127) / 128, C / cw);
+#define AZG_STEM_SYM(CC)                                                                                        \
+    case CC:                                                                                                    \
+        if (g_stem_variant == 1 && symmode == SYM_EACH) hipLaunchKernelGGL((stem_mfma<CC, EPI_BN_RELU, true, 0, false, SYM_EACH>), grid, dim3(256), 0, st, x, boards, players, ws, scale, shift, out, M, nullptr, nullptr, syms); \
+        else if (g_stem_variant == 1) hipLaunchKernelGGL((stem_mfma<CC, EPI_BN_RELU, true, 0, false, SYM_MEAN8>), grid, dim3(256), 0, st, x, boards, players, ws, scale, shift, out, M, nullptr, nullptr, syms); \
+        else if (symmode == SYM_EACH) hipLaunchKernelGGL((stem_conv<CC, EPI_BN_RELU, true, SYM_EACH>), dim3(B), dim3(256), 0, st, x, boards, players, ws, scale, shift, out, syms); \
+        else hipLaunchKernelGGL((stem_conv<CC, EPI_BN_RELU, true, SYM_MEAN8>), dim3(B), dim3(256), 0, st, x, boards, players, ws, scale, shift, out, syms); \
+        return hipGetLastError();
+        switch (C) {
+            AZG_STEM_SYM(64)
+            AZG_STEM_SYM(128)
+            AZG_STEM_SYM(256)
+            default: return hipErrorInvalidValue;
+        }
+#undef AZG_STEM_SYM
+    }
     if (g_stem_variant == 1) {
         const int M = B * PIX;
         const int cw = C < STEM_CW ? C : STEM_CW;

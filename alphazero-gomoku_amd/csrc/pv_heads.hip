@@ -163,6 +163,127 @@ __global__ __launch_bounds__(256) void heads_finalize(const float* __restrict__ 
     if (lane == 0) values[b] = tanhf(v);
 }
 
+// One image's head outputs, heads_finalize's arithmetic expression for expression: lane's
+// softmax probabilities pj[t] of squares j = lane + 64 t (0 past ACTIONS) and the value.
+__device__ __forceinline__ float finalize_image(const float* __restrict__ pb, const float* __restrict__ bpf,
+                                                const float* __restrict__ bv1, const float* __restrict__ wv2,
+                                                const float* __restrict__ bv2, int lane, float (&pj)[4])
+{
+    float lg[4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lane + 64 * t;
+        lg[t] = j < ACTIONS ? pb[j] + bpf[j] : -INFINITY;
+        mx = fmaxf(mx, lg[t]);
+    }
+    mx = wave_max(mx);
+    float e[4], sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lane + 64 * t;
+        e[t] = j < ACTIONS ? expf(lg[t] - mx) : 0.f;
+        sum += e[t];
+    }
+    sum = wave_sum(sum);
+    const float inv = 1.f / sum;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) pj[t] = e[t] * inv;
+    const float hid = fmaxf(pb[ACTIONS + lane] + bv1[lane], 0.f);
+    const float v = wave_sum(hid * wv2[lane]) + bv2[0];
+    return tanhf(v);
+}
+
+// heads_finalize under a symmetry per board (SYM_EACH): image b is board b seen through
+// syms[b] & 7, so the result for image square j belongs to board square q = sym_src(j, s).
+// Only the store address differs from heads_finalize (a permutation of the row: every
+// output element is written exactly once); boards is the caller's untransformed board.
+__global__ __launch_bounds__(256) void heads_finalize_sym(const float* __restrict__ pre, const float* __restrict__ bpf,
+                                                          const float* __restrict__ bv1,
+                                                          const float* __restrict__ wv2,
+                                                          const float* __restrict__ bv2, float* __restrict__ probs,
+                                                          float* __restrict__ values, int B,
+                                                          const int8_t* __restrict__ boards,
+                                                          float* __restrict__ priors,
+                                                          const int8_t* __restrict__ syms)
+{
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int s = (int)syms[b] & 7;
+    float pj[4];
+    const float v = finalize_image(pre + (size_t)b * FC_OUT, bpf, bv1, wv2, bv2, lane, pj);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lane + 64 * t;
+        if (j < ACTIONS) {
+            const int y = j / BOARD;
+            const int q = sym_src(y, j - y * BOARD, s);
+            probs[(size_t)b * ACTIONS + q] = pj[t];
+            if (priors) priors[(size_t)b * ACTIONS + q] = pj[t] * (boards[(size_t)b * PIX + q] == 0 ? 1.f : 0.f);
+        }
+    }
+    if (lane == 0) values[b] = v;
+}
+
+// The mean over a board's 8 images (SYM_MEAN8), one wave per board: image 8 b + s is board b
+// seen through symmetry s.  acc[sym_src(j, s)] += p_j in an LDS row per board -- within one s
+// the targets are a permutation (no two lanes collide), and the 8 additions per square happen
+// in s order from 0, plain float adds (no multiply to contract with): bitwise the host's
+// sequential float32 sum.  The value accumulates in a register in the same order.  Nothing
+// but the outputs is written, so a recompute is the same call again.
+__global__ __launch_bounds__(256) void heads_finalize_mean8(const float* __restrict__ pre,
+                                                            const float* __restrict__ bpf,
+                                                            const float* __restrict__ bv1,
+                                                            const float* __restrict__ wv2,
+                                                            const float* __restrict__ bv2, float* __restrict__ probs,
+                                                            float* __restrict__ values, int B,
+                                                            const int8_t* __restrict__ boards,
+                                                            float* __restrict__ priors)
+{
+#pragma clang fp contract(off)   // acc + p and vacc + v must stay plain adds (p = e * inv is a product)
+    __shared__ float accs[4][4 * 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wid;
+    if (b >= B) return;                     // wave-uniform; the kernel has no workgroup barrier
+    float* acc = accs[wid];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[lane + 64 * t] = 0.f;
+    float vacc = 0.f;
+    for (int s = 0; s < 8; ++s) {
+        // the row is wave-private: order this wave's LDS accesses of step s - 1 before step s
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float pj[4];
+        const float v = finalize_image(pre + ((size_t)b * 8 + s) * FC_OUT, bpf, bv1, wv2, bv2, lane, pj);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = lane + 64 * t;
+            if (j < ACTIONS) {
+                const int y = j / BOARD;
+                const int q = sym_src(y, j - y * BOARD, s);
+                acc[q] = acc[q] + pj[t];
+            }
+        }
+        vacc = vacc + v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int q = lane + 64 * t;
+        if (q < ACTIONS) {
+            const float p = acc[q] * 0.125f;
+            probs[(size_t)b * ACTIONS + q] = p;
+            if (priors) priors[(size_t)b * ACTIONS + q] = p * (boards[(size_t)b * PIX + q] == 0 ? 1.f : 0.f);
+        }
+    }
+    if (lane == 0) values[b] = vacc * 0.125f;
+}
+
 hipError_t launch_heads_project(int C, bool bn, const float* act, const float* wpc, const float* wvc,
                                 const float* hscale, const float* hshift, float* hout, int M, hipStream_t st,
                                 int fs, int voff)
@@ -194,9 +315,12 @@ hipError_t launch_heads_fwd(int C, const float* act, const float* wpc, const flo
                             const float* hshift, const float* wfc, const float* bpf,
                             const float* bv1, const float* wv2, const float* bv2, float* hbuf, float* probs,
                             float* values, float* logits, int B, hipStream_t st, const int8_t* boards,
-                            float* priors, bool projected)
+                            float* priors, bool projected, const int8_t* syms, int symmode)
 {
     if (B <= 0) return hipSuccess;
+    if (symmode != SYM_NONE && (logits || !boards || (symmode != SYM_EACH && symmode != SYM_MEAN8) ||
+                                (symmode == SYM_EACH && !syms) || (symmode == SYM_MEAN8 && B % 8 != 0)))
+        return hipErrorInvalidValue;
     // hbuf: [B][FC_FS] features (zero pads, set at allocation) then pre [B][FC_OUT]; the
     // board16 tower writes the features itself (projected)
     hipError_t e = projected ? hipSuccess
@@ -207,8 +331,15 @@ hipError_t launch_heads_fwd(int C, const float* act, const float* wpc, const flo
     hipLaunchKernelGGL(heads_fc, dim3((B + 31) / 32, 10), dim3(256), 0, st, hbuf, wfc, pre, B);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(heads_finalize, dim3((B + 3) / 4), dim3(256), 0, st, pre, bpf, bv1, wv2, bv2, probs, values,
-                       logits, B, boards, priors);
+    if (symmode == SYM_EACH)
+        hipLaunchKernelGGL(heads_finalize_sym, dim3((B + 3) / 4), dim3(256), 0, st, pre, bpf, bv1, wv2, bv2, probs,
+                           values, B, boards, priors, syms);
+    else if (symmode == SYM_MEAN8)   // B images = B / 8 boards
+        hipLaunchKernelGGL(heads_finalize_mean8, dim3((B / 8 + 3) / 4), dim3(256), 0, st, pre, bpf, bv1, wv2, bv2,
+                           probs, values, B / 8, boards, priors);
+    else
+        hipLaunchKernelGGL(heads_finalize, dim3((B + 3) / 4), dim3(256), 0, st, pre, bpf, bv1, wv2, bv2, probs, values,
+                           logits, B, boards, priors);
     return hipGetLastError();
 }
 

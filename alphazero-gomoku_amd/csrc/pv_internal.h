@@ -118,13 +118,17 @@ extern int g_tower_coh;
 #endif
 hipError_t launch_stem(int C, int epi, const float* x, const float* ws, const float* scale,
                        const float* shift, float* out, int B, hipStream_t st, const int8_t* boards = nullptr,
-                       const int8_t* players = nullptr);
+                       const int8_t* players = nullptr, const int8_t* syms = nullptr, int symmode = SYM_NONE);
+// symmode (pv_common.h SymMode) != SYM_NONE: B counts IMAGES (SYM_MEAN8: 8 per board) in the
+// stem, the projection and the fc; the finalize writes each board's outputs in the board's
+// own coordinates (SYM_MEAN8: the mean of its 8 images, B / 8 boards); logits must be null
 hipError_t launch_heads_fwd(int C, const float* act, const float* wpc, const float* wvc,
                             const float* hscale, const float* hshift, const float* wfc,
                             const float* bpf, const float* bv1,
                             const float* wv2, const float* bv2, float* hbuf, float* probs,
                             float* values, float* logits, int B, hipStream_t st,
-                            const int8_t* boards = nullptr, float* priors = nullptr, bool projected = false);
+                            const int8_t* boards = nullptr, float* priors = nullptr, bool projected = false,
+                            const int8_t* syms = nullptr, int symmode = SYM_NONE);
 hipError_t launch_heads_fc(const float* feat, const float* wfc, float* pre, int B, hipStream_t st);
 hipError_t launch_heads_project(int C, bool bn, const float* act, const float* wpc, const float* wvc,
                                 const float* hscale, const float* hshift, float* hout, int M, hipStream_t st,
@@ -224,6 +228,8 @@ struct azg_pv {
         int batch = 0;
         bool h3 = false;
         float *probs = nullptr, *values = nullptr, *logits = nullptr, *priors = nullptr;
+        const int8_t* syms = nullptr;   // azg_pv_forward_boards_sym: the symmetries and the mode
+        int symmode = azg::SYM_NONE;    // (batch counts boards, not images)
     };
     std::vector<LaunchRec> launches;
     uint32_t recovered = 0;           // launches recomputed per layer
@@ -261,5 +267,6 @@ hipError_t prof_harvest(azg_pv* h);
 void prof_end(azg_pv* h, int pair, hipStream_t st);
 int32_t forward_eval(azg_pv* h, const float* x, int batch, float* probs, float* values, float* logits,
                      hipStream_t st, const int8_t* boards, const int8_t* players, float* priors,
-                     bool per_layer = false, bool fp32_only = false, unsigned guard_seq = 0);
+                     bool per_layer = false, bool fp32_only = false, unsigned guard_seq = 0,
+                     const int8_t* syms = nullptr, int symmode = SYM_NONE);
 }  // namespace azg

@@ -10,20 +10,6 @@
 
 namespace azg {
 
-// Source square of output square (y, x) under symmetry s: with r = np.rot90(a, k),
-// r[y][x] = a[x][n-1-y] for k = 1 (and its powers); np.flip(r, columns)[y][x] = r[y][n-1-x].
-__device__ __forceinline__ int replay_src(int y, int x, int s)
-{
-    constexpr int n = BOARD;
-    if (s & 1) x = n - 1 - x;
-    switch (s >> 1) {
-    case 0: return y * n + x;
-    case 1: return x * n + (n - 1 - y);
-    case 2: return (n - 1 - y) * n + (n - 1 - x);
-    default: return (n - 1 - x) * n + y;
-    }
-}
-
 // One 256-thread workgroup per sample; thread j < 225 owns output square j (stores
 // coalesced along j; the loads are a permutation of one 225-element row).
 __global__ __launch_bounds__(256) void replay_gather_kernel(
@@ -41,7 +27,7 @@ __global__ __launch_bounds__(256) void replay_gather_kernel(
     const int j = threadIdx.x;
     if (j < PIX) {
         const int y = j / BOARD, xx = j - y * BOARD;
-        const int src = replay_src(y, xx, s);
+        const int src = sym_src(y, xx, s);   // pv_common.h
         const int8_t v = stones[(size_t)pos * PIX + src];
         float* xo = x + (size_t)b * 3 * PIX;
         xo[j] = v == 1 ? 1.f : 0.f;

@@ -26,6 +26,8 @@ class TowerFault(RuntimeError):
 
 
 class PolicyValueEngine:
+    MEAN8_MAX_BOARDS = 2048   # azg_pv_forward_boards_sym mode 1: boards per call (8 images each)
+
     def __init__(self, net: nn.Module, blocks: int, channels: int, board: int, device):
         if board != 15:
             raise ValueError("the gfx950 kernels are built for 15x15 boards only")
@@ -226,12 +228,28 @@ class PolicyValueEngine:
         check(self.lib.azg_pv_forward(self.h, ptr(x), int(x.shape[0]), ptr(probs), ptr(values), ptr(logits),
                                       _stream(self.device)), self.lib)
 
-    def forward_boards_into(self, boards, players, probs, values, priors=None):
+    def forward_boards_into(self, boards, players, probs, values, priors=None, syms=None, mean8=False):
         """Eval forward from device int8 boards [B,225] + players [B] (on-GPU encode);
-        priors (optional) = probs * (board == 0)."""
+        priors (optional) = probs * (board == 0).
+
+        syms (device int8 [B], values 0..7): board b is evaluated as its image syms[b]
+        (network.sym_table) and the results come back in the board's own coordinates.
+        mean8: every board is evaluated as all 8 images and the results are their mean
+        (B <= MEAN8_MAX_BOARDS).  Both run inside the stem and the heads' last kernel
+        (include/azg_pv.h azg_pv_forward_boards_sym); syms must stay intact until the
+        forward is settled, like boards.  With neither, the plain entry point runs."""
         self.sync_dirty()
-        check(self.lib.azg_pv_forward_boards(self.h, ptr(boards), ptr(players), int(boards.shape[0]), ptr(probs),
-                                             ptr(values), ptr(priors), _stream(self.device)), self.lib)
+        if syms is None and not mean8:
+            check(self.lib.azg_pv_forward_boards(self.h, ptr(boards), ptr(players), int(boards.shape[0]), ptr(probs),
+                                                 ptr(values), ptr(priors), _stream(self.device)), self.lib)
+            return
+        if syms is not None and not mean8:
+            if syms.dtype != torch.int8 or syms.device != boards.device or syms.numel() != boards.shape[0] \
+                    or not syms.is_contiguous():
+                raise ValueError("syms must be a contiguous int8 tensor [B] on the boards' device")
+        check(self.lib.azg_pv_forward_boards_sym(self.h, ptr(boards), ptr(players), None if mean8 else ptr(syms),
+                                                 1 if mean8 else 0, int(boards.shape[0]), ptr(probs), ptr(values),
+                                                 ptr(priors), _stream(self.device)), self.lib)
 
     def train_backward(self, x, pis, zs, losses):
         self.sync_dirty()

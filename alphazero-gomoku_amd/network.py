@@ -26,6 +26,63 @@ import torch.nn as nn
 
 from engine import PolicyValueEngine
 
+MEAN8_MAX_BOARDS = PolicyValueEngine.MEAN8_MAX_BOARDS   # boards per mean-of-8 forward (8 images each)
+_N = 15
+
+
+# ---------------- board symmetries (host helpers, numpy only) ----------------
+def sym_table() -> np.ndarray:
+    """[8, 225] int64: sym_table()[s, j] is the board square that image square j shows
+    under symmetry s -- the one convention of MCTS.symmetries, azg_pv_replay_gather and
+    azg_pv_forward_boards_sym (csrc/pv_common.h sym_src): np.rot90 by k = s >> 1
+    (counter-clockwise), then a column flip when s is odd.  image.flat[j] =
+    board.flat[table[s, j]]; a per-square result of the image at j belongs to board
+    square table[s, j]."""
+    n = _N
+    y, x = np.divmod(np.arange(n * n, dtype=np.int64), n)
+    t = np.empty((8, n * n), dtype=np.int64)
+    for s in range(8):
+        xs = n - 1 - x if s & 1 else x
+        k = s >> 1
+        t[s] = (y * n + xs if k == 0 else xs * n + (n - 1 - y) if k == 1
+                else (n - 1 - y) * n + (n - 1 - xs) if k == 2 else (n - 1 - xs) * n + y)
+    return t
+
+
+_SYM_TABLE = sym_table()
+
+
+def _check_sym(s) -> int:
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) <= 7:
+        raise ValueError(f"a symmetry is an int in 0..7, got {s!r}")
+    return int(s)
+
+
+def apply_symmetry(boards, s: int) -> np.ndarray:
+    """Image s of boards [..., 15, 15] or [..., 225] (any dtype), same shape."""
+    a = np.asarray(boards)
+    flat = a.reshape(-1, _N * _N) if a.size else a.reshape(0, _N * _N)
+    return flat[:, _SYM_TABLE[_check_sym(s)]].reshape(a.shape)
+
+
+def invert_symmetry(per_square, s: int) -> np.ndarray:
+    """Per-square results [..., 225] (or [..., 15, 15]) of image s back in the board's own
+    coordinates: out[..., table[s, j]] = per_square[..., j]."""
+    a = np.asarray(per_square)
+    flat = a.reshape(-1, _N * _N) if a.size else a.reshape(0, _N * _N)
+    out = np.empty_like(flat)
+    out[:, _SYM_TABLE[_check_sym(s)]] = flat
+    return out.reshape(a.shape)
+
+
+def _parse_leaf_symmetry(symmetry):
+    """Evaluator / proxy option -> None | int 0..7 | "random" | "mean8"."""
+    if symmetry is None or (isinstance(symmetry, str) and symmetry in ("random", "mean8")):
+        return symmetry
+    if isinstance(symmetry, str):
+        raise ValueError(f"symmetry must be None, an int 0..7, 'random' or 'mean8', got {symmetry!r}")
+    return _check_sym(symmetry)
+
 
 class ResidualBlock(nn.Module):
     """Parameter container of reference network.py:9-26 (compute: pv_conv.hip)."""
@@ -201,9 +258,21 @@ class BoardEvaluator:
     (the search writes int8 boards straight into it), non-blocking H2D, the
     board-input forward, non-blocking D2H of the masked priors and values, and an
     event to wait on.  Two evaluators let the host search one half of the games
-    while the GPU evaluates the other."""
+    while the GPU evaluates the other.
 
-    def __init__(self, model: "PyTorchModel", capacity: int):
+    symmetry: None (the plain forward), an int 0..7 (every leaf as that image),
+    "random" (a symmetry per leaf drawn from this evaluator's own Generator(seed) -- never
+    numpy's global RNG, whose Dirichlet and move-sampling streams stay where they are --
+    visible as ``syms[:n]`` after submit) or "mean8" (the mean over all 8 images, at most
+    MEAN8_MAX_BOARDS leaves per batch).  The transform runs inside the forward's kernels;
+    priors and values come back in the board's own coordinates."""
+
+    def __init__(self, model: "PyTorchModel", capacity: int, symmetry=None, seed=None):
+        self.symmetry = _parse_leaf_symmetry(symmetry)
+        if self.symmetry == "mean8" and int(capacity) > MEAN8_MAX_BOARDS:
+            raise ValueError(f"BoardEvaluator(symmetry='mean8'): capacity {int(capacity)} > {MEAN8_MAX_BOARDS}: a "
+                             f"mean-of-8 batch runs 8 images per board in ONE forward, and the engine takes at "
+                             f"most {MEAN8_MAX_BOARDS} boards (= {8 * MEAN8_MAX_BOARDS} images) per call")
         self.model = model
         dev = model.engine.device
         self.capacity = int(capacity)
@@ -221,6 +290,16 @@ class BoardEvaluator:
         self.event = torch.cuda.Event()
         self.n = 0
         self.seq = 0                             # tower launch number of the batch in flight
+        self.h_syms = self.d_syms = self.syms = self.rng = None
+        if self.symmetry is not None and self.symmetry != "mean8":
+            self.h_syms = torch.zeros((capacity,), dtype=torch.int8).pin_memory()
+            self.d_syms = torch.zeros((capacity,), dtype=torch.int8, device=dev)
+            self.syms = self.h_syms.numpy()      # the symmetries of the batch in flight
+            if self.symmetry == "random":
+                self.rng = np.random.Generator(np.random.PCG64(seed))
+            else:                                # a fixed image: set once
+                self.syms[:] = self.symmetry
+                self.d_syms.fill_(self.symmetry)
 
     def submit(self, n: int) -> None:
         self.n = n
@@ -229,8 +308,16 @@ class BoardEvaluator:
         self.d_boards[:n].copy_(self.h_boards[:n], non_blocking=True)
         self.d_players[:n].copy_(self.h_players[:n], non_blocking=True)
         eng = self.model.engine
-        eng.forward_boards_into(self.d_boards[:n], self.d_players[:n], self.d_probs[:n],
-                                self.d_values[:n], self.d_priors[:n])
+        if self.symmetry is not None:
+            if self.rng is not None:
+                self.syms[:n] = self.rng.integers(0, 8, size=n, dtype=np.int8)
+                self.d_syms[:n].copy_(self.h_syms[:n], non_blocking=True)
+            eng.forward_boards_into(self.d_boards[:n], self.d_players[:n], self.d_probs[:n], self.d_values[:n],
+                                    self.d_priors[:n], syms=None if self.d_syms is None else self.d_syms[:n],
+                                    mean8=self.symmetry == "mean8")
+        else:
+            eng.forward_boards_into(self.d_boards[:n], self.d_players[:n], self.d_probs[:n],
+                                    self.d_values[:n], self.d_priors[:n])
         self.seq = eng.last_seq()
         self.h_priors[:n].copy_(self.d_priors[:n], non_blocking=True)
         self.h_values[:n].copy_(self.d_values[:n], non_blocking=True)
@@ -312,10 +399,33 @@ class PyTorchModel:
 
     policy_value = predict
 
-    def predict_boards(self, boards: np.ndarray, players: np.ndarray, masked: bool = True):
+    def predict_boards(self, boards: np.ndarray, players: np.ndarray, masked: bool = True, symmetry=None):
         """Leaf evaluation from int8 boards [B,15,15] or [B,225] and the side to move
         [B]: the encoding (games/gomoku.py:130-150) runs inside the stem kernel.
-        Returns (priors = probs * valid if masked else probs, values [B,1]) as numpy."""
+        Returns (priors = probs * valid if masked else probs, values [B,1]) as numpy.
+
+        symmetry: None; an int 0..7 or an int array [B] (board b is evaluated as its image
+        symmetry[b], sym_table()); or "mean8" (the mean over all 8 images, summed in image
+        order; batches above MEAN8_MAX_BOARDS boards run as successive calls).  The
+        transform runs on the GPU and the results are in the board's own coordinates:
+        bitwise apply_symmetry -> plain predict_boards -> invert_symmetry."""
+        n_boards = len(boards)
+        syms_np = None
+        if symmetry is not None and not (isinstance(symmetry, str) and symmetry == "mean8"):
+            if isinstance(symmetry, str):
+                raise ValueError(f"symmetry must be None, an int 0..7, an int array [B] or 'mean8', got {symmetry!r}")
+            if np.ndim(symmetry) == 0:
+                syms_np = np.full(n_boards, _check_sym(symmetry if not isinstance(symmetry, np.ndarray)
+                                                       else symmetry.item()), dtype=np.int8)
+            else:
+                a = np.asarray(symmetry)
+                if a.dtype.kind not in "iu" or a.shape != (n_boards,):
+                    raise ValueError(f"symmetry array must be integers of shape [{n_boards}], got "
+                                     f"{a.dtype} {a.shape}")
+                if a.size and (a.min() < 0 or a.max() > 7):
+                    raise ValueError("symmetry array values must be in 0..7")
+                syms_np = np.ascontiguousarray(a, dtype=np.int8)
+        mean8 = symmetry is not None and syms_np is None
         eng = self.engine
         b = torch.from_numpy(np.ascontiguousarray(boards, dtype=np.int8).reshape(len(boards), 225)).to(eng.device)
         pl = torch.from_numpy(np.ascontiguousarray(players, dtype=np.int8).reshape(-1)).to(eng.device)
@@ -323,16 +433,34 @@ class PyTorchModel:
         probs = torch.empty((B, 225), dtype=torch.float32, device=eng.device)
         values = torch.empty((B, 1), dtype=torch.float32, device=eng.device)
         priors = torch.empty_like(probs) if masked else None
-        eng.forward_boards_into(b, pl, probs, values, priors)
-        seq = eng.last_seq()
-        out = (priors if masked else probs).cpu().numpy(), values.cpu().numpy()
-        if eng.recover(seq):
+        if symmetry is None:
+            eng.forward_boards_into(b, pl, probs, values, priors)
+            seq = eng.last_seq()
             out = (priors if masked else probs).cpu().numpy(), values.cpu().numpy()
+            if eng.recover(seq):
+                out = (priors if masked else probs).cpu().numpy(), values.cpu().numpy()
+            eng.check_orphans()
+            return out
+        sy = None if mean8 else torch.from_numpy(syms_np).to(eng.device)
+        step = MEAN8_MAX_BOARDS if mean8 else max(B, 1)
+        for lo in range(0, B, step):   # each call is settled before the next reuses the workspace
+            hi = min(B, lo + step)
+            eng.forward_boards_into(b[lo:hi], pl[lo:hi], probs[lo:hi], values[lo:hi],
+                                    None if priors is None else priors[lo:hi],
+                                    syms=None if mean8 else sy[lo:hi], mean8=mean8)
+            seq = eng.last_seq()
+            torch.cuda.current_stream(eng.device).synchronize()
+            eng.recover(seq)
+        out = (priors if masked else probs).cpu().numpy(), values.cpu().numpy()
         eng.check_orphans()
         return out
 
-    def board_evaluator(self, capacity: int) -> "BoardEvaluator":
-        return BoardEvaluator(self, capacity)
+    def board_evaluator(self, capacity: int, symmetry=None, seed=None) -> "BoardEvaluator":
+        return BoardEvaluator(self, capacity, symmetry=symmetry, seed=seed)
+
+    def symmetric(self, symmetry, seed=None) -> "SymmetricModel":
+        """This model with leaf evaluation under board symmetries (SymmetricModel)."""
+        return SymmetricModel(self, symmetry, seed=seed)
 
     def predict_batch(self, states_list: list) -> Tuple[np.ndarray, np.ndarray]:
         return self.predict(self.make_batch_from_states(states_list))
@@ -440,3 +568,55 @@ class PyTorchModel:
     @staticmethod
     def make_batch_from_states(list_of_encoded_states: list) -> np.ndarray:
         return np.stack(list_of_encoded_states, axis=0).astype(np.float32)
+
+
+class SymmetricModel:
+    """A light proxy of a PyTorchModel whose leaf evaluations run under board symmetries:
+    ``symmetry`` is an int 0..7, "random" (a symmetry per leaf, AlphaGo Zero's leaf
+    evaluation) or "mean8" (the mean over all 8 images: exactly equivariant, 8x the cost).
+    Self-play, gating and the players only call ``board_evaluator`` / ``predict``, so the
+    proxy drops into selfplay_games, NativeSelfPlay, NativeEval, evaluate_models and
+    NativeMCTS unchanged; everything else (net, engine, save, ...) is the model's.
+
+    seed: evaluator number k of a seeded proxy draws from Generator([seed, k]); predict
+    draws from Generator(seed).  A position is evaluated once per tree node, so its
+    symmetry is drawn once."""
+
+    def __init__(self, model: PyTorchModel, symmetry, seed=None):
+        sym = _parse_leaf_symmetry(symmetry)
+        if sym is None:
+            raise ValueError("SymmetricModel needs a symmetry: an int 0..7, 'random' or 'mean8'")
+        self.__dict__.update(_model=model, symmetry=sym, seed=seed, _evaluators=0,
+                             rng=np.random.Generator(np.random.PCG64(seed)) if sym == "random" else None)
+
+    def __getattr__(self, name):          # everything not defined here: the model's
+        return getattr(self._model, name)
+
+    def __setattr__(self, name, value):
+        if name in self.__dict__:
+            self.__dict__[name] = value
+        else:
+            setattr(self._model, name, value)
+
+    def board_evaluator(self, capacity: int) -> BoardEvaluator:
+        k = self._evaluators
+        self._evaluators = k + 1
+        seed = None if self.seed is None else [self.seed, k]
+        return BoardEvaluator(self._model, capacity, symmetry=self.symmetry, seed=seed)
+
+    def predict(self, encoded_states: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """PyTorchModel.predict on float planes [B,3,15,15] (plane 0: the side to move's
+        stones, plane 1: the opponent's): the planes become int8 stones (plane0 + 2 plane1,
+        player 1) and the board forward applies the symmetry on the GPU."""
+        x = np.asarray(encoded_states, dtype=np.float32)
+        stones = (x[:, 0] + 2.0 * x[:, 1]).astype(np.int8).reshape(len(x), 225)
+        players = np.ones(len(x), dtype=np.int8)
+        sym = self.symmetry
+        if sym == "random":
+            sym = self.rng.integers(0, 8, size=len(x), dtype=np.int8)
+        return self._model.predict_boards(stones, players, masked=False, symmetry=sym)
+
+    policy_value = predict
+
+    def predict_batch(self, states_list: list) -> Tuple[np.ndarray, np.ndarray]:
+        return self.predict(self._model.make_batch_from_states(states_list))

@@ -22,7 +22,7 @@ from mcts.native_mcts import NativeMCTS
 
 class AlphaPlayer:
     def __init__(self, rules="gomoku", board_size=15, n_simulations=5000, c_puct=1.0, model_path=None,
-                 nn_model=None, mcts_kwargs=None, mcts_class=None):
+                 nn_model=None, mcts_kwargs=None, mcts_class=None, leaf_symmetry=None):
         if nn_model is None:
             from network import PyTorchModel
             nn_model = PyTorchModel
@@ -42,7 +42,10 @@ class AlphaPlayer:
             raise ValueError(f"Unsupported rules: {self.rules}. Only 'gomoku' is supported.")
         self.game_class = Gomoku
         mcts_class = mcts_class or NativeMCTS
-        self.mcts = mcts_class(game_class=self.game_class, n_simulations=self.n_simulations, nn_model=self.net,
+        # leaf_symmetry (None, an int 0..7, "random" or "mean8"): the search's leaves are
+        # evaluated under board symmetries (network.SymmetricModel)
+        search_net = self.net if leaf_symmetry is None else self.net.symmetric(leaf_symmetry)
+        self.mcts = mcts_class(game_class=self.game_class, n_simulations=self.n_simulations, nn_model=search_net,
                          cpuct=self.c_puct, add_dirichlet_noise=False, **(mcts_kwargs or {}))
 
     def play(self, board, turn_number, last_opponent_move):

@@ -146,7 +146,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     next_iteration_continuation: int = 1, dirichlet_alpha: float = 0.03,
                     dirichlet_epsilon: float = 0.25, dirichlet_n_moves: int = 30, n_res_blocks: int = 3,
                     channels: int = 64, device: Optional[str] = None, max_moves: Optional[int] = None,
-                    device_buffer: bool = False, **reference_worker_kwargs):
+                    device_buffer: bool = False, leaf_symmetry=None, eval_symmetry=None,
+                    **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -154,7 +155,12 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     device_buffer=True keeps the replay buffer on the GPU (replay.DeviceReplayBuffer):
     self-play hands over canonical positions only, every batch is gathered (encoding +
     dihedral image) by a HIP kernel, and the step reads it in place.  Same batches, same
-    model and same buffer pickle as the default host deque under the same seeds."""
+    model and same buffer pickle as the default host deque under the same seeds.
+
+    leaf_symmetry / eval_symmetry (None, an int 0..7, "random" or "mean8"): evaluate the
+    leaves of self-play, respectively of both gating models, under board symmetries
+    (network.SymmetricModel; the transform runs inside the forward's kernels).  None, the
+    default, is the loop without them, bit for bit."""
     r, w, _, dev = D.init_from_env()
     device = device or str(dev)
     main = r == 0
@@ -191,7 +197,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             print(f"\n=== ITER {it}/{last}: self-play (games={games_per_iteration}, sims={n_simulations}, "
                   f"ranks={w}) {datetime.now():%Y-%m-%d %H:%M:%S} ===")
         n_local = len(D.shard(games_per_iteration))
-        examples, winners, drv = selfplay_games(model_candidate, GameClass, n_local, n_simulations, cpuct, temp_fn,
+        sp_model = model_candidate if leaf_symmetry is None else model_candidate.symmetric(leaf_symmetry)
+        examples, winners, drv = selfplay_games(sp_model, GameClass, n_local, n_simulations, cpuct, temp_fn,
                                                 dirichlet_alpha, dirichlet_epsilon, dirichlet_n_moves,
                                                 max_moves=max_moves, board_size=board_size,
                                                 use_symmetries=host_symmetries)
@@ -224,7 +231,9 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
 
         te = time.time()
         try:
-            new_wins, win_rate, draws = evaluate_models(model_candidate, model_best, game_name, n_games=eval_games,
+            ev_new, ev_best = ((model_candidate, model_best) if eval_symmetry is None else
+                               (model_candidate.symmetric(eval_symmetry), model_best.symmetric(eval_symmetry)))
+            new_wins, win_rate, draws = evaluate_models(ev_new, ev_best, game_name, n_games=eval_games,
                                                         n_simulations=eval_mcts_simulations, cpuct=cpuct)
         except TowerFault:
             # a forward that computed on stale inputs and could not be recomputed: an

@@ -106,6 +106,32 @@ int32_t azg_pv_forward(azg_pv* h, const float* x, int32_t batch,
 int32_t azg_pv_forward_boards(azg_pv* h, const int8_t* boards, const int8_t* players, int32_t batch,
                               float* probs, float* values, float* priors, void* stream);
 
+/* azg_pv_forward_boards under board symmetries.  Symmetry s in 0..7 is the one of
+ * MCTS.symmetries (mcts/new_mcts_alpha.py:42-56) and of azg_pv_replay_gather: np.rot90 by
+ * k = s >> 1 (counter-clockwise), then a column flip when s is odd.  The net sees the
+ * image; the result for an image square is returned at the board square it came from, and
+ * the value is untouched.  The transform costs no extra pass: the stem reads the board
+ * through the square permutation and the heads' last kernel stores through its inverse.
+ * mode 0: board b is evaluated as its image syms[b] (device int8 [batch], values 0..7;
+ *         a value outside is taken & 7; syms == NULL means all 0 and is bitwise
+ *         azg_pv_forward_boards).  probs / values / priors come back in the BOARD's
+ *         own coordinates, bitwise what transforming on the host, azg_pv_forward_boards
+ *         and transforming back give.
+ * mode 1: every board is evaluated as all 8 images (8*batch images in one forward) and
+ *         probs / values are their mean, summed in image order 0..7 and scaled by 1/8
+ *         (bitwise the sequential float32 sum of the 8 mode-0 results); syms is
+ *         ignored.  batch <= 2048.
+ * priors (optional): probs * (board == 0) on the caller's untransformed board.
+ * Checked first, before the bound check and any device call: null handle, mode not 0 or
+ * 1, negative batch, batch > 2048 in mode 1, null boards / players / probs / values with
+ * batch > 0.  batch 0 returns 0.
+ * Like boards and players, the caller's syms buffer must stay intact until the forward
+ * is settled: azg_pv_recover recomputes a posted launch from the same boards, players and
+ * syms with the same symmetry handling into the same outputs. */
+int32_t azg_pv_forward_boards_sym(azg_pv* h, const int8_t* boards, const int8_t* players,
+                                  const int8_t* syms, int32_t mode, int32_t batch,
+                                  float* probs, float* values, float* priors, void* stream);
+
 /* Train-mode forward + loss + backward on the local batch (reference
  * network.py:213-222).  Writes d(loss)/d(param) into the bound grad buffer
  * (overwrites: zero_grad semantics), updates BN running stats (momentum 0.1,
