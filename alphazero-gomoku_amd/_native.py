@@ -6,6 +6,7 @@ fallback.  If it is missing or cannot load, importing the product raises.
 from __future__ import annotations
 
 import ctypes
+import enum
 import os
 
 import torch  # noqa: F401  -- load torch's HIP runtime first so the library binds to it
@@ -85,6 +86,41 @@ PROF_CLASSES = ("conv3x3", "stem", "heads", "train_conv", "train_wgrad", "train_
                 "board16")
 ABI_VERSION = 3   # 2: tower launch numbers, azg_pv_recover, the wait record (round 5); 3: the gradient
                   # buffer's skip word, azg_pv_train_fp32_once, azg_pv_posted (round 6)
+
+
+class TUNE(enum.IntEnum):
+    """Keys of azg_pv_set_tuning: include/azg_pv.h enum azg_pv_tuning_key, without the prefix."""
+    CONV_SHAPE = 0
+    CONV_AUTOTUNE = 1
+    QUERY_CONV_SHAPE = 2
+    CONV_ABLATION = 3
+    CONV_STAGING = 4
+    TOWER_MODE = 5
+    TOWER_SHAPE = 6
+    ABLATION_SHAPE = 7
+    TOWER_ABLATION = 8
+    STEM_KERNEL = 9
+    TOWER_BODY = 10
+    STEM_ABLATION = 11
+    TOWER_WAIT_US = 14
+    QUERY_STUDY_BUILD = 15
+    TOWER_CLAIM = 17
+    BREAKER_SECONDS = 18
+    EVAL_ARITH = 19
+    H3_TOWER_BODY = 20
+    CONV_TAIL_SPLIT = 21
+    CONV_BODY = 22
+    TRAIN_FUSE_APPLY = 23
+    TRAIN_FUSE_FINALIZE = 24
+    WGRAD_SPLITS = 27
+    TOWER_SC1_LOADS = 31
+    TRAIN_APPLY_GRID = 44
+    WGRAD_TILE = 48
+    TRAIN_ARITH = 49
+    TRAIN_DGRAD_ARITH = 50
+    BOARD_ABLATION = 51
+    BOARD16_SPLIT_MAX = 52
+
 
 _lib = None
 

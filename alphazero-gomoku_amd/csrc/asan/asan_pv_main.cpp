@@ -120,14 +120,15 @@ int main()
         CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 2, 8, nullptr, 1, &f, &f, &f, nullptr) != 0);
     }
     // tuning keys round-trip (previous value returned)
-    const int prev = azg_pv_set_tuning(5, 0);
-    CHECK(azg_pv_set_tuning(5, prev) == 0);
+    const int prev = azg_pv_set_tuning(AZG_PV_TUNE_TOWER_MODE, 0);
+    CHECK(azg_pv_set_tuning(AZG_PV_TUNE_TOWER_MODE, prev) == 0);
     CHECK(azg_pv_set_tuning(999, 1) == -1);
-    const int prev_wait = azg_pv_set_tuning(14, 0);   // wait bound (us): default 1 s
+    const int prev_wait = azg_pv_set_tuning(AZG_PV_TUNE_TOWER_WAIT_US, 0);   // wait bound (us): default 100 ms
     CHECK(prev_wait == 100000);
-    CHECK(azg_pv_set_tuning(14, -1) == 0 && azg_pv_set_tuning(14, -1) == 100000);
-    const int prev_breaker = azg_pv_set_tuning(18, 0);   // breaker seconds: default 30
-    CHECK(prev_breaker == 30 && azg_pv_set_tuning(18, prev_breaker) == 0);
+    CHECK(azg_pv_set_tuning(AZG_PV_TUNE_TOWER_WAIT_US, -1) == 0);
+    CHECK(azg_pv_set_tuning(AZG_PV_TUNE_TOWER_WAIT_US, -1) == 100000);
+    const int prev_breaker = azg_pv_set_tuning(AZG_PV_TUNE_BREAKER_SECONDS, 0);   // breaker seconds: default 30
+    CHECK(prev_breaker == 30 && azg_pv_set_tuning(AZG_PV_TUNE_BREAKER_SECONDS, prev_breaker) == 0);
     std::printf("asan_pv: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;
 }

@@ -44,6 +44,17 @@ static int32_t fail(const char* what, hipError_t e = hipSuccess)
         if (_e != hipSuccess) return fail(what, _e); \
     } while (0)
 
+// hipMalloc of a buffer that lives as long as the handle: azg_pv_destroy frees the list
+template <class T>
+static hipError_t handle_malloc(azg_pv* h, T** p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) h->dev_allocs.push_back(*p);
+    return e;
+}
+
+static int32_t run_eval(azg_pv* h, const EvalCall& c, void* stream);
+
 extern "C" {
 
 int32_t azg_pv_abi_version(void) { return 3; }
@@ -74,18 +85,8 @@ int32_t azg_pv_destroy(azg_pv* h)
     if (!h) return 0;
     if (h->wbase) (void)hipDeviceSynchronize();
     free_workspace(h);
-    if (h->wbase) (void)hipFree(h->wbase);
-    if (h->bn_desc_dev) (void)hipFree(h->bn_desc_dev);
-    if (h->conv_off_dev) (void)hipFree(h->conv_off_dev);
+    for (void* p : h->dev_allocs) (void)hipFree(p);
     if (h->ring_host) (void)hipHostFree(h->ring_host);
-    if (h->tower_diag) (void)hipFree(h->tower_diag);
-    if (h->b16x) (void)hipFree(h->b16x);
-    if (h->b16flag) (void)hipFree(h->b16flag);
-    if (h->wpack16) (void)hipFree(h->wpack16);
-    if (h->scale16) (void)hipFree(h->scale16);
-    if (h->h3exp) (void)hipFree(h->h3exp);
-    if (h->h3inv) (void)hipFree(h->h3inv);
-    if (h->conv_bn_off_dev) (void)hipFree(h->conv_bn_off_dev);
     for (auto& e : h->prof_ev) (void)hipEventDestroy(e);
     delete h;
     return 0;
@@ -116,7 +117,7 @@ int32_t azg_pv_bind(azg_pv* h, float* params, float* grads, float* bn_stats)
         floats += (size_t)FC_OUT * FC_KP;          // wfc
         floats += (size_t)h->nfold * 2;            // scale, shift
         float* base = nullptr;
-        hipError_t e = hipMalloc(&base, floats * sizeof(float));
+        hipError_t e = handle_malloc(h, &base, floats * sizeof(float));
         if (e != hipSuccess) return fail("azg_pv_bind: hipMalloc(packed weights)", e);
         h->wbase = base;
         h->wpack = base; base += (size_t)2 * h->NB * 9 * C * C;
@@ -124,7 +125,7 @@ int32_t azg_pv_bind(azg_pv* h, float* params, float* grads, float* bn_stats)
         h->wfc = base; base += (size_t)FC_OUT * FC_KP;
         h->scale = base; base += h->nfold;
         h->shift = base; base += h->nfold;
-        e = hipMalloc(&h->bn_desc_dev, sizeof(BnDesc) * h->bn_desc.size());
+        e = handle_malloc(h, &h->bn_desc_dev, sizeof(BnDesc) * h->bn_desc.size());
         if (e == hipSuccess)
             e = hipMemcpy(h->bn_desc_dev, h->bn_desc.data(), sizeof(BnDesc) * h->bn_desc.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail("azg_pv_bind: bn descriptor upload", e);
@@ -133,7 +134,7 @@ int32_t azg_pv_bind(azg_pv* h, float* params, float* grads, float* bn_stats)
             offs[2 * i] = h->poff[h->t_blk[i].w1];
             offs[2 * i + 1] = h->poff[h->t_blk[i].w2];
         }
-        e = hipMalloc(&h->conv_off_dev, sizeof(int64_t) * offs.size());
+        e = handle_malloc(h, &h->conv_off_dev, sizeof(int64_t) * offs.size());
         if (e == hipSuccess)
             e = hipMemcpy(h->conv_off_dev, offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail("azg_pv_bind: conv offset upload", e);
@@ -151,7 +152,7 @@ int32_t azg_pv_bind(azg_pv* h, float* params, float* grads, float* bn_stats)
         h->ring_dev = (unsigned*)dp;
         h->ovf_dev = h->ring_dev + kTowerRing;
         h->train_ovf_dev = h->ring_dev + 2 * kTowerRing;
-        e = hipMalloc(&h->tower_diag, kTowerDiagWords * sizeof(unsigned));
+        e = handle_malloc(h, &h->tower_diag, kTowerDiagWords * sizeof(unsigned));
         if (e == hipSuccess) e = hipMemset(h->tower_diag, 0, kTowerDiagWords * sizeof(unsigned));
         if (e != hipSuccess) return fail("azg_pv_bind: tower wait record", e);
         h->launches.assign(kTowerRing, azg_pv::LaunchRec{});
@@ -191,13 +192,13 @@ int32_t azg_pv_forward(azg_pv* h, const float* x, int32_t batch, float* probs, f
     if (batch < 0) return fail("azg_pv_forward: negative batch");
     if (batch == 0) return 0;            // empty batch: nothing to do (empty tensors have null data)
     if (!x || !probs || !values) return fail("azg_pv_forward: null x/probs/values");
-    hipStream_t st = (hipStream_t)stream;
-    if (int32_t r = ensure_eval_workspace(h, batch, st)) return r;
-    if (h->dirty) {
-        if (int32_t r = repack(h, st)) return r;
-        h->dirty = false;
-    }
-    return forward_eval(h, x, batch, probs, values, logits, st, nullptr, nullptr, nullptr);
+    EvalCall c;
+    c.x = x;
+    c.batch = batch;
+    c.probs = probs;
+    c.values = values;
+    c.logits = logits;
+    return run_eval(h, c, stream);
 }
 
 int32_t azg_pv_forward_boards(azg_pv* h, const int8_t* boards, const int8_t* players, int32_t batch, float* probs,
@@ -208,13 +209,14 @@ int32_t azg_pv_forward_boards(azg_pv* h, const int8_t* boards, const int8_t* pla
     if (batch < 0) return fail("azg_pv_forward_boards: negative batch");
     if (batch == 0) return 0;
     if (!boards || !players || !probs || !values) return fail("azg_pv_forward_boards: null boards/players/probs/values");
-    hipStream_t st = (hipStream_t)stream;
-    if (int32_t r = ensure_eval_workspace(h, batch, st)) return r;
-    if (h->dirty) {
-        if (int32_t r = repack(h, st)) return r;
-        h->dirty = false;
-    }
-    return forward_eval(h, nullptr, batch, probs, values, nullptr, st, boards, players, priors);
+    EvalCall c;
+    c.boards = boards;
+    c.players = players;
+    c.batch = batch;
+    c.probs = probs;
+    c.values = values;
+    c.priors = priors;
+    return run_eval(h, c, stream);
 }
 
 int32_t azg_pv_forward_boards_sym(azg_pv* h, const int8_t* boards, const int8_t* players, const int8_t* syms,
@@ -233,16 +235,16 @@ int32_t azg_pv_forward_boards_sym(azg_pv* h, const int8_t* boards, const int8_t*
     if (h->cfg.board != BOARD || h->cfg.in_ch != 3)
         return fail("azg_pv_forward_boards_sym: needs a 15x15, 3-plane net");
     if (batch == 0) return 0;
-    const int symmode = mode == 1 ? SYM_MEAN8 : syms ? SYM_EACH : SYM_NONE;   // no syms: the plain forward
-    const int images = symmode == SYM_MEAN8 ? 8 * batch : batch;
-    hipStream_t st = (hipStream_t)stream;
-    if (int32_t r = ensure_eval_workspace(h, images, st)) return r;
-    if (h->dirty) {
-        if (int32_t r = repack(h, st)) return r;
-        h->dirty = false;
-    }
-    return forward_eval(h, nullptr, batch, probs, values, nullptr, st, boards, players, priors, false, false, 0u,
-                        symmode == SYM_EACH ? syms : nullptr, symmode);
+    EvalCall c;
+    c.boards = boards;
+    c.players = players;
+    c.symmode = mode == 1 ? SYM_MEAN8 : syms ? SYM_EACH : SYM_NONE;   // no syms: the plain forward
+    c.syms = c.symmode == SYM_EACH ? syms : nullptr;
+    c.batch = batch;
+    c.probs = probs;
+    c.values = values;
+    c.priors = priors;
+    return run_eval(h, c, stream);
 }
 
 int32_t azg_pv_profile_enable(azg_pv* h, int32_t enable)
@@ -357,18 +359,20 @@ int32_t azg_pv_recover(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream
     __atomic_store_n(h->ovf_host + slot, 0u, __ATOMIC_RELEASE);
     hipStream_t rst = (hipStream_t)stream;
     const bool guard = !ovf && r.h3;
-    if (int32_t e = forward_eval(h, r.x, r.batch, r.probs, r.values, r.logits, rst, r.boards, r.players, r.priors,
-                                 true, ovf, guard ? seq : 0u, r.syms, r.symmode))
-        return e;
+    EvalOpts redo;
+    redo.per_layer = true;
+    redo.fp32_only = ovf;
+    redo.guard_seq = guard ? seq : 0u;
+    if (int32_t e = forward_eval(h, r.call, rst, redo)) return e;
     bool late_ovf = false;
     if (guard) {
         AZG_TRY(hipStreamSynchronize(rst), "azg_pv_recover: sync");
         late_ovf = __atomic_load_n(h->ovf_host + slot, __ATOMIC_ACQUIRE) == seq;
         if (late_ovf) {
             __atomic_store_n(h->ovf_host + slot, 0u, __ATOMIC_RELEASE);
-            if (int32_t e = forward_eval(h, r.x, r.batch, r.probs, r.values, r.logits, rst, r.boards, r.players,
-                                         r.priors, true, true, 0u, r.syms, r.symmode))
-                return e;
+            redo.fp32_only = true;
+            redo.guard_seq = 0u;
+            if (int32_t e = forward_eval(h, r.call, rst, redo)) return e;
         }
     }
     if (late_ovf) ++h->h3_overflows;
@@ -425,10 +429,6 @@ int32_t azg_pv_tower_diag_read(azg_pv* h, azg_pv_tower_diag* out, void* stream)
     out->producer_start_us = (int32_t)w[22] / 100;
     out->max_wall_us = us(w[23]);
     out->waits_suspended = w[24];
-    out->breaker_trips = h->breaker_trips;
-    out->breaker_launches = h->breaker_launches;
-    out->h3_overflows = h->h3_overflows;
-    out->train_h3_overflows = train_skips(h);
     return 0;
 }
 
@@ -453,6 +453,22 @@ int32_t azg_pv_tower_diag_clear(azg_pv* h, void* stream)
 namespace azg {
 
 int32_t set_error(const char* what, hipError_t e) { return fail(what, e); }
+}  // namespace azg
+
+// The shared tail of the public forwards (their argument checks done): workspace for the
+// call's images, the packs of the current parameters, the forward.
+static int32_t run_eval(azg_pv* h, const EvalCall& c, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (int32_t r = ensure_eval_workspace(h, c.images(), st)) return r;
+    if (h->dirty) {
+        if (int32_t r = repack(h, st)) return r;
+        h->dirty = false;
+    }
+    return forward_eval(h, c, st);
+}
+
+namespace azg {
 
 // Fold every recorded event pair into the per-class sums (waits for them).
 hipError_t prof_harvest(azg_pv* h)
@@ -544,40 +560,41 @@ void build_layout(azg_pv* h)
     h->bn_val = addbn(h->t_vbn_g, h->t_vbn_b, 1);
     h->nbn = stat;
     h->nfold = fold;
+    h->conv_bn_off.assign(NB > 0 ? 2 * NB : 1, 0);
+    for (int i = 0; i < NB; ++i) {
+        h->conv_bn_off[2 * i] = h->bn_desc[h->bn_blk[i].first].out_off;
+        h->conv_bn_off[2 * i + 1] = h->bn_desc[h->bn_blk[i].second].out_off;
+    }
+}
+
+// the eval workspace (sized by act_cap images): activations, head features, tower records
+static void free_eval_workspace(azg_pv* h)
+{
+    for (int i = 0; i < 3; ++i) {
+        if (h->act[i]) (void)hipFree(h->act[i]);
+        h->act[i] = nullptr;
+    }
+    if (h->hbuf) (void)hipFree(h->hbuf);
+    h->hbuf = nullptr;
+    if (h->tower_sync) (void)hipFree(h->tower_sync);
+    h->tower_sync = nullptr;
+    if (h->tower_prod) (void)hipFree(h->tower_prod);
+    h->tower_prod = nullptr;
+    h->act_cap = 0;
 }
 
 void free_workspace(azg_pv* h)
 {
-    for (int i = 0; i < 3; ++i) {
-        if (h->act[i]) (void)hipFree(h->act[i]);
-        h->act[i] = nullptr;
-    }
-    if (h->hbuf) (void)hipFree(h->hbuf);
-    h->hbuf = nullptr;
-    if (h->tower_sync) (void)hipFree(h->tower_sync);
-    h->tower_sync = nullptr;
-    if (h->tower_prod) (void)hipFree(h->tower_prod);
-    h->tower_prod = nullptr;
-    h->act_cap = 0;
+    free_eval_workspace(h);
     free_train_workspace(h);
 }
 
-int32_t ensure_eval_workspace(azg_pv* h, int batch, hipStream_t st)
+int32_t ensure_eval_workspace(azg_pv* h, int images, hipStream_t st)
 {
-    if (batch <= h->act_cap) return 0;
+    if (images <= h->act_cap) return 0;
     int cap = h->act_cap ? h->act_cap : 64;
-    while (cap < batch) cap *= 2;
-    for (int i = 0; i < 3; ++i) {
-        if (h->act[i]) (void)hipFree(h->act[i]);
-        h->act[i] = nullptr;
-    }
-    if (h->hbuf) (void)hipFree(h->hbuf);
-    h->hbuf = nullptr;
-    if (h->tower_sync) (void)hipFree(h->tower_sync);
-    h->tower_sync = nullptr;
-    if (h->tower_prod) (void)hipFree(h->tower_prod);
-    h->tower_prod = nullptr;
-    h->act_cap = 0;
+    while (cap < images) cap *= 2;
+    free_eval_workspace(h);
     {
         hipError_t e = hipMalloc(&h->tower_sync, tower_sync_bytes(2 * h->NB, cap * PIX));
         if (e != hipSuccess) return fail("ensure_eval_workspace: hipMalloc(tower sync)", e);
@@ -618,26 +635,18 @@ int32_t repack(azg_pv* h, hipStream_t st, float* dgrad_dst, int part)
     return 0;
 }
 
-// Stem + residual tower.  variant 0: one launch per conv; 5 / 8 / 10: the persistent
-// tower (pv_tower.hip) with 64x64 / 128x64 / 128x128 (16-wave) tiles.  All bitwise
-// identical.
 // The split-fp16 (H3) eval weights of the current parameters (pv_pack.hip pack_h3):
 // allocated on first use, re-packed after every repack.
 int32_t ensure_h3(azg_pv* h, hipStream_t st)
 {
     const int C = h->C, nl = 2 * h->NB;
     if (!h->wpack16) {
-        const BnDesc* bd = h->bn_desc.data();
-        std::vector<int> off(nl > 0 ? nl : 1, 0);
-        for (int i = 0; i < h->NB; ++i) {
-            off[2 * i] = bd[h->bn_blk[i].first].out_off;
-            off[2 * i + 1] = bd[h->bn_blk[i].second].out_off;
-        }
-        hipError_t e = hipMalloc(&h->wpack16, (size_t)(nl > 0 ? nl : 1) * 9 * C * C * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&h->scale16, (size_t)h->nfold * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&h->h3exp, (size_t)(nl > 0 ? nl : 1) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc(&h->h3inv, (size_t)(nl > 0 ? nl : 1) * C * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&h->conv_bn_off_dev, off.size() * sizeof(int));
+        const std::vector<int>& off = h->conv_bn_off;
+        hipError_t e = handle_malloc(h, &h->wpack16, (size_t)(nl > 0 ? nl : 1) * 9 * C * C * sizeof(float));
+        if (e == hipSuccess) e = handle_malloc(h, &h->scale16, (size_t)h->nfold * sizeof(float));
+        if (e == hipSuccess) e = handle_malloc(h, &h->h3exp, (size_t)(nl > 0 ? nl : 1) * sizeof(int));
+        if (e == hipSuccess) e = handle_malloc(h, &h->h3inv, (size_t)(nl > 0 ? nl : 1) * C * sizeof(float));
+        if (e == hipSuccess) e = handle_malloc(h, &h->conv_bn_off_dev, off.size() * sizeof(int));
         if (e == hipSuccess) e = hipMemcpy(h->conv_bn_off_dev, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail("forward: split-fp16 weight buffers", e);
         h->h3_dirty = true;
@@ -655,158 +664,168 @@ int32_t ensure_h3(azg_pv* h, hipStream_t st)
 // H3 per-layer tile: the 64x64 / 4-wave tile (shape 5, up to 4 workgroups per CU) or the
 // 128x64 / 8-wave tile (shape 8, 2 per CU), whichever needs fewer 128-row-equivalent
 // rounds of resident slots (ties: the 128-row tile).  Both compute the same arithmetic.
-static int conv_tuned_shape_h3(azg_pv* h, int batch, hipStream_t, const float*, const int8_t*, const int8_t*)
+static int conv_tuned_shape_h3(const azg_pv* h, int images)
 {
-    if (g_conv_shape_override == 5 || g_conv_shape_override == 8) return g_conv_shape_override;   // key 0
-    const int M = batch * PIX, ntn = h->C / 64;
+    if (g_conv_shape_override == 5 || g_conv_shape_override == 8) return g_conv_shape_override;   // CONV_SHAPE
+    const int M = images * PIX, ntn = h->C / 64;
     const long t5 = (long)((M + 63) / 64) * ntn, t8 = (long)((M + 127) / 128) * ntn;
     const long r5 = (t5 + 1023) / 1024, r8 = (t8 + 511) / 512;
     return r5 < 2 * r8 ? 5 : 8;
 }
 
-static int32_t stem_and_tower(azg_pv* h, int variant, const float* x, int batch, hipStream_t st,
-                              const int8_t* boards, const int8_t* players, float** out, unsigned seq = 0,
-                              bool h3 = false, bool recompute = false, const int8_t* syms = nullptr,
-                              int symmode = SYM_NONE)
+// How one forward runs its residual tower (forward_eval decides, the autotuner tries each).
+struct TowerPlan {
+    int variant = 0;          // see stem_and_tower
+    bool h3 = false;          // split-fp16 residual convs
+    unsigned seq = 0;         // the launch's number (0: not posted)
+    bool recompute = false;   // azg_pv_recover's rerun: must not wait across workgroups
+};
+
+// The heads' 1x1 projection weights and folded BN: policy (2 channels) then value (1), contiguous.
+struct HeadProj { const float *wpc, *wvc, *scale, *shift; };
+static HeadProj head_proj(const azg_pv* h)
 {
-    // symmode != SYM_NONE: batch counts images (the stem reads them through the symmetries)
-    const int C = h->C;
-    const int M = batch * PIX;
-    const BnDesc* bd = h->bn_desc.data();
-    int pr = prof_begin(h, AZG_PROF_STEM, st, batch);
-    AZG_TRY(launch_stem(C, EPI_BN_RELU, x, h->wstem, h->scale + bd[h->bn_stem].out_off,
-                        h->shift + bd[h->bn_stem].out_off, h->act[0], batch, st, boards, players, syms, symmode),
+    const int ho = h->bn_desc[h->bn_pol].out_off;
+    return {h->params + h->poff[h->t_pc_w], h->params + h->poff[h->t_vc_w], h->scale + ho, h->shift + ho};
+}
+
+static int32_t stem(azg_pv* h, const EvalCall& c, hipStream_t st)
+{
+    const int o = h->bn_desc[h->bn_stem].out_off;
+    const int pr = prof_begin(h, AZG_PROF_STEM, st, c.images());
+    AZG_TRY(launch_stem(h->C, EPI_BN_RELU, c.x, h->wstem, h->scale + o, h->shift + o, h->act[0], c.images(), st,
+                        c.boards, c.players, c.syms, c.symmode),
             "forward: stem");
     prof_end(h, pr, st);
+    return 0;
+}
+
+// The exchange buffers of a split board16 launch (allocated on first use) and its flag epoch.
+static int32_t next_b16_split(azg_pv* h, hipStream_t st, Board16Split* sp)
+{
+    if (!h->b16x) {
+        AZG_TRY(handle_malloc(h, &h->b16x, (size_t)kB16SplitCap * 2 * kB16ImgBytes), "forward: split images");
+        AZG_TRY(handle_malloc(h, &h->b16flag, (size_t)kB16SplitCap * 3 * sizeof(unsigned)), "forward: split flags");
+        AZG_TRY(hipMemsetAsync(h->b16x, 0, (size_t)kB16SplitCap * 2 * kB16ImgBytes, st), "forward: split images");
+        h->b16epoch = 1u << 25;   // forces the flag reset below
+    }
+    if (++h->b16epoch >= 1u << 25) {   // tags epoch * 64 + layer stay monotonic: restart them at 1
+        AZG_TRY(hipMemsetAsync(h->b16flag, 0, (size_t)kB16SplitCap * 3 * sizeof(unsigned), st), "forward: split flags");
+        h->b16epoch = 1;
+    }
+    *sp = Board16Split{h->b16x, h->b16flag, h->b16epoch, h->ring_dev, h->tower_diag};
+    return 0;
+}
+
+// The board-resident tower (pv_board.hip, pv_board16.hip; variants 13 and 14): every conv of
+// one board from LDS, the tower output in place over the stem output in act[0].
+static int32_t board_tower(azg_pv* h, int images, hipStream_t st, const TowerPlan& p)
+{
+    const bool b16 = p.variant == 14;
+    const int* off = h->conv_bn_off.data();
     float* X = h->act[0];
-    float* H = h->act[1];
-    float* Y = h->act[2];
-    if ((variant == 13 || variant == 14) && h->NB > 0) {
-        // the board-resident tower (pv_board.hip): every conv of one board from LDS,
-        // the tower output in place over the stem output
-        int out_off[2 * kTowerMaxBlocks];
-        for (int i = 0; i < h->NB; ++i) {
-            out_off[2 * i] = bd[h->bn_blk[i].first].out_off;
-            out_off[2 * i + 1] = bd[h->bn_blk[i].second].out_off;
-        }
-        // key 19 = 2: small batches run split (three workgroups per board, heads unfused; not
-        // for a recompute, which must not wait across workgroups), the rest one workgroup per
-        // board with the heads' projections fused (features into hbuf, forward_eval)
-        // a one-workgroup launch of B = k * grid + r boards ends with r boards on r CUs: for
-        // r <= key 52 those r run split after the k full rounds (their heads projected here)
-        const int smax = variant == 14 && !recompute ? board16_split_max() : 0;
-        const int grid = variant == 14 ? board16_grid() : 0;
-        const int tail = variant == 14 && batch > grid && grid > 0 && batch % grid <= smax ? batch % grid : 0;
-        h->b16_split = variant == 14 && batch <= smax;
-        // one hipEvent bracket per tower launch (the tail's is a second board16 launch)
-        pr = prof_begin(h, variant == 14 ? AZG_PROF_BOARD16 : AZG_PROF_BOARD, st, batch - tail);
-        if (h->b16_split || tail) {
-            if (!h->b16x) {
-                AZG_TRY(hipMalloc(&h->b16x, (size_t)kB16SplitCap * 2 * kB16ImgBytes), "forward: split images");
-                AZG_TRY(hipMalloc(&h->b16flag, (size_t)kB16SplitCap * 3 * sizeof(unsigned)), "forward: split flags");
-                AZG_TRY(hipMemsetAsync(h->b16x, 0, (size_t)kB16SplitCap * 2 * kB16ImgBytes, st), "forward: split images");
-                h->b16epoch = 1u << 25;   // forces the flag reset below
-            }
-            if (++h->b16epoch >= 1u << 25) {   // tags epoch * 64 + layer stay monotonic: restart them at 1
-                AZG_TRY(hipMemsetAsync(h->b16flag, 0, (size_t)kB16SplitCap * 3 * sizeof(unsigned), st),
-                        "forward: split flags");
-                h->b16epoch = 1;
-            }
-            const Board16Split sp{h->b16x, h->b16flag, h->b16epoch, h->ring_dev, h->tower_diag};
-            if (tail) {   // the k full rounds one workgroup per board, heads fused
-                const float* P = h->params;
-                const int ho = bd[h->bn_pol].out_off, nmain = batch - tail;
-                const float *wpc = P + h->poff[h->t_pc_w], *wvc = P + h->poff[h->t_vc_w];
-                AZG_TRY(launch_board16_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, out_off, X, nmain,
-                                             h->ovf_dev, seq, st, wpc, wvc, h->scale + ho, h->shift + ho, h->hbuf),
-                        "forward: board tower (16x16x32)");
-                prof_end(h, pr, st);
-                float* Xt = X + (size_t)nmain * PADPIX * C;
-                pr = prof_begin(h, AZG_PROF_BOARD16, st, tail);
-                AZG_TRY(launch_board16_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, out_off, Xt, tail,
-                                             h->ovf_dev, seq, st, nullptr, nullptr, nullptr, nullptr, nullptr, &sp),
-                        "forward: board tower (16x16x32, split tail)");
-                prof_end(h, pr, st);
-                pr = prof_begin(h, AZG_PROF_HEADS, st, 0);
-                AZG_TRY(launch_heads_project(C, true, Xt, wpc, wvc, h->scale + ho, h->shift + ho,
-                                             h->hbuf + (size_t)nmain * FC_FS, tail * PIX, st, FC_FS, FC_KP),
-                        "forward: heads projection (split tail)");
-            } else {
-                AZG_TRY(launch_board16_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, out_off, X,
-                                             batch, h->ovf_dev, seq, st, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                             &sp),
-                        "forward: board tower (16x16x32, split)");
-            }
-        } else if (variant == 14) {
-            const float* P = h->params;
-            const int ho = bd[h->bn_pol].out_off;
-            AZG_TRY(launch_board16_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, out_off, X, batch,
-                                         h->ovf_dev, seq, st, P + h->poff[h->t_pc_w], P + h->poff[h->t_vc_w],
-                                         h->scale + ho, h->shift + ho, h->hbuf),
-                    "forward: board tower (16x16x32)");
-        } else
-            AZG_TRY(launch_board_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, out_off, X, batch,
-                                       h->ovf_dev, seq, st),
-                    "forward: board tower");
-        prof_end(h, pr, st);
-        *out = X;
-        return 0;
-    }
-    if (variant != 0 && h->NB > 0) {
-        // the whole residual tower in one persistent launch
-        int out_off[2 * kTowerMaxBlocks];
-        for (int i = 0; i < h->NB; ++i) {
-            out_off[2 * i] = bd[h->bn_blk[i].first].out_off;
-            out_off[2 * i + 1] = bd[h->bn_blk[i].second].out_off;
-        }
-        pr = prof_begin(h, variant == 10 || variant == 12 ? AZG_PROF_TOWER_WIDE : AZG_PROF_TOWER, st, batch);
-        const TowerSync ts{h->tower_sync, h->ring_dev, h->ovf_dev, h->tower_diag, h->tower_prod, seq};
-        AZG_TRY(launch_tower(C, h->NB, variant, h->act, h3 ? (const float*)h->wpack16 : h->wpack,
-                             h3 ? h->scale16 : h->scale, h->shift, out_off, M, ts, st, &X, h3),
-                "forward: tower");
-        prof_end(h, pr, st);
-        *out = X;
-        return 0;
-    }
-    if (h3) {   // split-fp16 per-layer convs: the tower's arithmetic, layer by layer
-        const int shape = conv_tuned_shape_h3(h, batch, st, x, boards, players);
-        const float* wp16 = (const float*)h->wpack16;
-        for (int i = 0; i < h->NB; ++i) {
-            const BnDesc& b1 = bd[h->bn_blk[i].first];
-            const BnDesc& b2 = bd[h->bn_blk[i].second];
-            pr = prof_begin(h, AZG_PROF_CONV3X3, st, batch);
-            AZG_TRY(launch_conv3x3_h3(shape, C, EPI_BN_RELU, X, wp16 + (size_t)(2 * i) * 9 * C * C,
-                                      h->scale16 + b1.out_off, h->shift + b1.out_off, nullptr, H, M, st, h->ovf_dev,
-                                      seq),
-                    "forward: conv1 (H3)");
+    // EVAL_ARITH = 2: small batches run split (three workgroups per board, heads unfused; not
+    // for a recompute, which must not wait across workgroups), the rest one workgroup per
+    // board with the heads' projections fused (features into hbuf, forward_eval)
+    // a one-workgroup launch of B = k * grid + r boards ends with r boards on r CUs: for
+    // r <= BOARD16_SPLIT_MAX those r run split after the k full rounds (their heads projected here)
+    const int smax = b16 && !p.recompute ? board16_split_max() : 0;
+    const int grid = b16 ? board16_grid() : 0;
+    const int tail = b16 && images > grid && grid > 0 && images % grid <= smax ? images % grid : 0;
+    h->b16_split = b16 && images <= smax;
+    // one hipEvent bracket per tower launch (the tail's is a second board16 launch)
+    int pr = prof_begin(h, b16 ? AZG_PROF_BOARD16 : AZG_PROF_BOARD, st, images - tail);
+    const HeadProj hp = head_proj(h);
+    // one workgroup per board with the heads fused (sp null), or split with the heads left out
+    auto tower16 = [&](float* x, int n, const Board16Split* sp) {
+        const bool fused = sp == nullptr;
+        return launch_board16_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, off, x, n, h->ovf_dev, p.seq,
+                                    st, fused ? hp.wpc : nullptr, fused ? hp.wvc : nullptr, fused ? hp.scale : nullptr,
+                                    fused ? hp.shift : nullptr, fused ? h->hbuf : nullptr, sp);
+    };
+    if (!b16) {
+        AZG_TRY(launch_board_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, off, X, images, h->ovf_dev,
+                                   p.seq, st),
+                "forward: board tower");
+    } else if (!h->b16_split && !tail) {
+        AZG_TRY(tower16(X, images, nullptr), "forward: board tower (16x16x32)");
+    } else {
+        Board16Split sp{};
+        if (int32_t r = next_b16_split(h, st, &sp)) return r;
+        if (!tail) {
+            AZG_TRY(tower16(X, images, &sp), "forward: board tower (16x16x32, split)");
+        } else {   // the k full rounds one workgroup per board, heads fused
+            const int nmain = images - tail;
+            AZG_TRY(tower16(X, nmain, nullptr), "forward: board tower (16x16x32)");
             prof_end(h, pr, st);
-            pr = prof_begin(h, AZG_PROF_CONV3X3, st, batch);
-            AZG_TRY(launch_conv3x3_h3(shape, C, EPI_BN_RES_RELU, H, wp16 + (size_t)(2 * i + 1) * 9 * C * C,
-                                      h->scale16 + b2.out_off, h->shift + b2.out_off, X, Y, M, st, h->ovf_dev, seq),
-                    "forward: conv2 (H3)");
+            float* Xt = X + (size_t)nmain * PADPIX * h->C;
+            pr = prof_begin(h, AZG_PROF_BOARD16, st, tail);
+            AZG_TRY(tower16(Xt, tail, &sp), "forward: board tower (16x16x32, split tail)");
             prof_end(h, pr, st);
-            float* t = X; X = Y; Y = t;
+            pr = prof_begin(h, AZG_PROF_HEADS, st, 0);
+            AZG_TRY(launch_heads_project(h->C, true, Xt, hp.wpc, hp.wvc, hp.scale, hp.shift,
+                                         h->hbuf + (size_t)nmain * FC_FS, tail * PIX, st, FC_FS, FC_KP),
+                    "forward: heads projection (split tail)");
         }
-        *out = X;
-        return 0;
     }
+    prof_end(h, pr, st);
+    return 0;
+}
+
+// The whole residual tower in one persistent launch of tiles (pv_tower.hip).
+static int32_t tile_tower(azg_pv* h, int images, hipStream_t st, const TowerPlan& p, float** out)
+{
+    const bool wide = p.variant == 10 || p.variant == 12;
+    const int pr = prof_begin(h, wide ? AZG_PROF_TOWER_WIDE : AZG_PROF_TOWER, st, images);
+    const TowerSync ts{h->tower_sync, h->ring_dev, h->ovf_dev, h->tower_diag, h->tower_prod, p.seq};
+    AZG_TRY(launch_tower(h->C, h->NB, p.variant, h->act, p.h3 ? (const float*)h->wpack16 : h->wpack,
+                         p.h3 ? h->scale16 : h->scale, h->shift, h->conv_bn_off.data(), images * PIX, ts, st, out,
+                         p.h3),
+            "forward: tower");
+    prof_end(h, pr, st);
+    return 0;
+}
+
+// One launch per conv: fp32 MFMA, or the split-fp16 tile (the tower's arithmetic, layer by layer).
+static int32_t per_layer_tower(azg_pv* h, int images, hipStream_t st, const TowerPlan& p, float** out)
+{
+    const int C = h->C, M = images * PIX;
+    const int shape = p.h3 ? conv_tuned_shape_h3(h, images) : 0;
+    const float* wp = p.h3 ? (const float*)h->wpack16 : h->wpack;
+    const float* scale = p.h3 ? h->scale16 : h->scale;
+    auto conv = [&](int l, int epi, const float* in, const float* resid, float* dst) {
+        const int o = h->conv_bn_off[l];
+        const float* w = wp + (size_t)l * 9 * C * C;
+        const int pr = prof_begin(h, AZG_PROF_CONV3X3, st, images);
+        const hipError_t e =
+            p.h3 ? launch_conv3x3_h3(shape, C, epi, in, w, scale + o, h->shift + o, resid, dst, M, st, h->ovf_dev, p.seq)
+                 : launch_conv3x3(C, epi, in, w, scale + o, h->shift + o, resid, dst, M, st);
+        if (e == hipSuccess) prof_end(h, pr, st);
+        return e;
+    };
+    float *X = h->act[0], *H = h->act[1], *Y = h->act[2];
     for (int i = 0; i < h->NB; ++i) {
-        const BnDesc& b1 = bd[h->bn_blk[i].first];
-        const BnDesc& b2 = bd[h->bn_blk[i].second];
-        pr = prof_begin(h, AZG_PROF_CONV3X3, st, batch);
-        AZG_TRY(launch_conv3x3(C, EPI_BN_RELU, X, h->wpack + (size_t)(2 * i) * 9 * C * C, h->scale + b1.out_off,
-                               h->shift + b1.out_off, nullptr, H, M, st),
-                "forward: conv1");
-        prof_end(h, pr, st);
-        pr = prof_begin(h, AZG_PROF_CONV3X3, st, batch);
-        AZG_TRY(launch_conv3x3(C, EPI_BN_RES_RELU, H, h->wpack + (size_t)(2 * i + 1) * 9 * C * C,
-                               h->scale + b2.out_off, h->shift + b2.out_off, X, Y, M, st),
-                "forward: conv2");
-        prof_end(h, pr, st);
+        AZG_TRY(conv(2 * i, EPI_BN_RELU, X, nullptr, H), "forward: conv1");
+        AZG_TRY(conv(2 * i + 1, EPI_BN_RES_RELU, H, X, Y), "forward: conv2");
         float* t = X; X = Y; Y = t;
     }
     *out = X;
     return 0;
+}
+
+// Stem + residual tower.  variant 0: one launch per conv; 5 / 8 / 10 / 12: the persistent
+// tower (pv_tower.hip) with 64x64 / 128x64 / 128x128 (16-wave) / h3_tile tiles; 13 / 14: the
+// board-resident tower on 32x32x16 / 16x16x32 MFMAs.  Within one arithmetic all are bitwise
+// identical.  *out: the activation buffer that holds the tower output.
+static int32_t stem_and_tower(azg_pv* h, const EvalCall& c, hipStream_t st, const TowerPlan& p, float** out)
+{
+    if (int32_t r = stem(h, c, st)) return r;
+    if ((p.variant == 13 || p.variant == 14) && h->NB > 0) {
+        *out = h->act[0];
+        return board_tower(h, c.images(), st, p);
+    }
+    if (p.variant != 0 && h->NB > 0) return tile_tower(h, c.images(), st, p, out);
+    return per_layer_tower(h, c.images(), st, p, out);
 }
 
 // Tower variant per (C, blocks, batch bucket): g_tower_mode 0 = per-layer launches,
@@ -821,9 +840,9 @@ static int32_t stem_and_tower(azg_pv* h, int variant, const float* x, int batch,
 // algorithmic HBM bytes instead of 1.76x) is measured slower at every batch (83.6 %)
 // and is not a candidate; key 6 = 10 forces it.  While the stream is being captured
 // the untuned default is used.  All variants are bitwise identical.
-static int tower_variant(azg_pv* h, const float* x, int batch, hipStream_t st, const int8_t* boards,
-                         const int8_t* players, bool h3, const int8_t* syms = nullptr, int symmode = SYM_NONE)
+static int tower_variant(azg_pv* h, const EvalCall& c, hipStream_t st, bool h3)
 {
+    const int batch = c.images();   // what the stem and the tower process
     if (h->NB == 0 || h->NB > kTowerMaxBlocks) return 0;
     if ((size_t)batch * PADPIX * h->C * sizeof(float) >= (size_t)INT32_MAX) return 0;
     if (g_tower_mode == 0) return 0;
@@ -856,18 +875,17 @@ static int tower_variant(azg_pv* h, const float* x, int batch, hipStream_t st, c
             bool ok = true;
             float* out = nullptr;
             for (int r = 0; r < 3 && ok; ++r)
-                for (int c = 0; c < ncand && ok; ++c) {
+                for (int k = 0; k < ncand && ok; ++k) {
                     ok = hipEventRecord(e0, st) == hipSuccess &&
-                         stem_and_tower(h, cand[c], x, batch, st, boards, players, &out, 0, h3, false, syms,
-                                        symmode) == 0 &&
+                         stem_and_tower(h, c, st, TowerPlan{cand[k], h3}, &out) == 0 &&
                          hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
                     float ms = 0.f;
-                    if (ok && r > 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < best_ms[c]) best_ms[c] = ms;
+                    if (ok && r > 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms < best_ms[k]) best_ms[k] = ms;
                 }
             if (ok) {
                 int b = 0;
-                for (int c = 1; c < ncand; ++c)
-                    if (best_ms[c] < best_ms[b]) b = c;
+                for (int k = 1; k < ncand; ++k)
+                    if (best_ms[k] < best_ms[b]) b = k;
                 if (batch >= 128 && best_ms[2] <= 1.02f * best_ms[b]) b = 2;   // the 128x64 tower
                 if (h3 && batch >= 128 && best_ms[3] < 0.98f * best_ms[b]) b = 3;   // unless h3_tile beats it by 2 %
                 if (board_ok && best_ms[4] < 0.98f * best_ms[b]) b = 4;            // or the board tower does
@@ -887,55 +905,51 @@ static int tower_variant(azg_pv* h, const float* x, int batch, hipStream_t st, c
     return choice;
 }
 
-int32_t forward_eval(azg_pv* h, const float* x, int batch, float* probs, float* values, float* logits,
-                     hipStream_t st, const int8_t* boards, const int8_t* players, float* priors, bool per_layer,
-                     bool fp32_only, unsigned guard_seq, const int8_t* syms, int symmode)
+int32_t forward_eval(azg_pv* h, const EvalCall& c, hipStream_t st, const EvalOpts& o)
 {
-    // `batch` boards; under SYM_MEAN8 the stem, the tower and the heads' fc see 8 images each
-    const int boards_n = batch;
-    if (symmode == SYM_MEAN8) batch *= 8;
     const int C = h->C;
     const float* P = h->params;
-    const BnDesc* bd = h->bn_desc.data();
-    // split-fp16 residual convs (key 19, C = 128 / 256): every path of the forward -- tower,
+    // split-fp16 residual convs (EVAL_ARITH, C = 128 / 256): every path of the forward -- tower,
     // per-layer, the autotuner's candidates, a recompute -- then computes the same arithmetic
-    const bool h3 = g_tower_h3 != 0 && !fp32_only && (C == 128 || C == 256) && h->NB > 0;
-    if (h3)
+    TowerPlan p;
+    p.recompute = o.per_layer;
+    p.h3 = g_tower_h3 != 0 && !o.fp32_only && (C == 128 || C == 256) && h->NB > 0;
+    if (p.h3)
         if (int32_t r = ensure_h3(h, st)) return r;
-    // key 19 = 2 at C = 128: the 16x16x32 board tower is the one form of its arithmetic, for
-    // every batch and path (it has no cross-workgroup waits: nothing for the breaker to avoid)
-    const bool k32 = h3 && g_tower_h3 == 2 && C == 128 && h->NB <= kTowerMaxBlocks;
-    int variant = k32 ? 14 : per_layer ? 0 : tower_variant(h, x, batch, st, boards, players, h3, syms, symmode);
-    if (variant != 0 && !k32 && h->breaker_until > 0.0) {
+    // EVAL_ARITH = 2 at C = 128: the 16x16x32 board tower is the one form of its arithmetic, for
+    // every batch and path (it has no cross-workgroup waits: nothing for the breaker to avoid;
+    // known defect, ADVICE.md: its split form does wait and still ignores the breaker)
+    const bool k32 = p.h3 && g_tower_h3 == 2 && C == 128 && h->NB <= kTowerMaxBlocks;
+    p.variant = k32 ? 14 : o.per_layer ? 0 : tower_variant(h, c, st, p.h3);
+    if (p.variant != 0 && !k32 && h->breaker_until > 0.0) {
         if (now_s() < h->breaker_until) {
-            variant = 0;
+            p.variant = 0;
             ++h->breaker_launches;
         } else {
             h->breaker_until = 0.0;
         }
     }
-    // a tower or H3 launch gets a number and a record of its buffers (azg_pv_recover);
+    // a tower or H3 launch gets a number and a record of its call (azg_pv_recover);
     // a recompute (per_layer) posts nothing
-    unsigned seq = per_layer ? guard_seq : 0u;
-    if ((variant != 0 || h3) && h->NB > 0 && !h->launches.empty() && !per_layer) {
-        seq = ++h->seq;
-        if (seq == 0) seq = ++h->seq;   // 0 means "not posted"
-        azg_pv::LaunchRec& r = h->launches[seq & (kTowerRing - 1)];
-        r = azg_pv::LaunchRec{seq, x, boards, players, boards_n, h3, probs, values, logits, priors, syms, symmode};
-        __atomic_store_n(h->ring_host + (seq & (kTowerRing - 1)), 0u, __ATOMIC_RELEASE);
-        __atomic_store_n(h->ovf_host + (seq & (kTowerRing - 1)), 0u, __ATOMIC_RELEASE);
+    p.seq = o.per_layer ? o.guard_seq : 0u;
+    if ((p.variant != 0 || p.h3) && h->NB > 0 && !h->launches.empty() && !o.per_layer) {
+        p.seq = ++h->seq;
+        if (p.seq == 0) p.seq = ++h->seq;   // 0 means "not posted"
+        const unsigned slot = p.seq & (kTowerRing - 1);
+        h->launches[slot] = azg_pv::LaunchRec{p.seq, p.h3, c};
+        __atomic_store_n(h->ring_host + slot, 0u, __ATOMIC_RELEASE);
+        __atomic_store_n(h->ovf_host + slot, 0u, __ATOMIC_RELEASE);
     }
-    if (!per_layer) h->last_seq = seq;
+    if (!o.per_layer) h->last_seq = p.seq;
     float* X = nullptr;
     h->b16_split = false;
-    if (int32_t r = stem_and_tower(h, variant, x, batch, st, boards, players, &X, seq, h3, per_layer, syms, symmode))
-        return r;
-    const int ho = bd[h->bn_pol].out_off;   // policy (2) then value (1): contiguous
-    int pr = prof_begin(h, AZG_PROF_HEADS, st, batch);
-    AZG_TRY(launch_heads_fwd(C, X, P + h->poff[h->t_pc_w], P + h->poff[h->t_vc_w], h->scale + ho, h->shift + ho,
-                             h->wfc, P + h->poff[h->t_pfc_b], P + h->poff[h->t_vfc1_b],
-                             P + h->poff[h->t_vfc2_w], P + h->poff[h->t_vfc2_b], h->hbuf, probs, values, logits,
-                             batch, st, boards, priors, variant == 14 && !h->b16_split, syms, symmode),
+    if (int32_t r = stem_and_tower(h, c, st, p, &X)) return r;
+    const HeadProj hp = head_proj(h);
+    const int pr = prof_begin(h, AZG_PROF_HEADS, st, c.images());
+    AZG_TRY(launch_heads_fwd(C, X, hp.wpc, hp.wvc, hp.scale, hp.shift, h->wfc, P + h->poff[h->t_pfc_b],
+                             P + h->poff[h->t_vfc1_b], P + h->poff[h->t_vfc2_w], P + h->poff[h->t_vfc2_b], h->hbuf,
+                             c.probs, c.values, c.logits, c.images(), st, c.boards, c.priors,
+                             p.variant == 14 && !h->b16_split, c.syms, c.symmode),
             "forward: heads");
     prof_end(h, pr, st);
     return 0;

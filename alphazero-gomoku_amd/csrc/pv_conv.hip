@@ -1061,182 +1061,3 @@ hipError_t launch_stem(int C, int epi, const float* x, const float* ws, const fl
 }
 
 }  // namespace azg
-
-namespace azg { extern int g_board_abl; }
-extern "C" int32_t azg_pv_set_tuning(int32_t key, int32_t value)
-{
-#ifdef AZG_AB_STUDIES
-    if (key == 51) {  // board-tower timing ablations (study build only)
-        const int prev = azg::g_board_abl;
-        azg::g_board_abl = value;
-        return prev;
-    }
-#endif
-    if (key == 0) {
-        const int prev = azg::g_conv_shape_override;
-        azg::g_conv_shape_override = value;
-        return prev;
-    }
-    if (key == 1) {
-        const int prev = azg::g_conv_autotune;
-        azg::g_conv_autotune = value;
-        return prev;
-    }
-    if (key == 3) {   // ablation mask (timing studies only, C=128 EPI_BN_RELU launches)
-        const int prev = azg::g_conv_ablation;
-#ifdef AZG_AB_STUDIES   // timing studies only: the product library ignores it
-        azg::g_conv_ablation = value;
-#endif
-        return prev;
-    }
-    if (key == 14) {  // persistent-tower dependency wait bound in us of awake time (-1 restores the default, 0 forces timeouts)
-        const int prev = (int)azg::g_tower_wait_us;
-        azg::g_tower_wait_us = value < 0 ? azg::kTowerWaitUs : (unsigned)value;
-        return prev;
-    }
-    if (key == 31) {  // study build only: 64x64 / 128x64 tower with sc1 dependent loads instead of the acquire
-#ifdef AZG_AB_STUDIES   // outside the guide's measured envelope (two or more workgroups per CU): never in the product
-        const int prev = azg::g_tower_coh;
-        azg::g_tower_coh = value ? 1 : 0;
-        return prev;
-#else
-        return 0;
-#endif
-    }
-    if (key == 48) {  // train weight-grad tile: 1 v2 (row table, buffer LDS-DMA, MFMA-layout slabs; default), 0 v1; bitwise identical
-        const int prev = azg::g_wgrad_variant;
-        if (value == 0 || value == 1) azg::g_wgrad_variant = value;
-        return prev;
-    }
-    if (key == 20) {  // H3 tower body: 1 = VAR 99 (board-keyed halo swizzle, default), 0 = VAR 98 (row-keyed); bitwise identical
-        const int prev = azg::g_h3_tower_var;
-        if (value == 0 || value == 1) azg::g_h3_tower_var = value;
-        return prev;
-    }
-    if (key == 49) {  // train forward convs: 1 split-fp16 products (H3), 0 fp32 MFMA
-        const int prev = azg::g_train_h3;
-        if (value >= 0 && value <= 2) azg::g_train_h3 = value;
-        return prev;
-    }
-    if (key == 50) {  // train dgrad convs: 2 split-fp16, four products; 1 three; 0 fp32 MFMA (default)
-        const int prev = azg::g_train_dgrad_h3;
-        if (value >= 0 && value <= 2) azg::g_train_dgrad_h3 = value;
-        return prev;
-    }
-    if (key == 52) {  // board16: largest batch run split (three workgroups per board; 0 never)
-        const int prev = azg::g_board16_split;
-        if (value >= 0) azg::g_board16_split = value;
-        return prev;
-    }
-    if (key == 19) {  // eval residual-conv arithmetic: 2 split-fp16 on 16x16x32 (default), 1 on 32x32x16, 0 fp32
-        const int prev = azg::g_tower_h3;
-        if (value == 0 || value == 1 || value == 2) azg::g_tower_h3 = value;
-        return prev;
-    }
-    if (key == 18) {  // seconds of per-layer convs after a recovered tower launch (0: off)
-        const int prev = azg::g_tower_breaker_s;
-        if (value >= 0) azg::g_tower_breaker_s = value;
-        return prev;
-    }
-    if (key == 17) {  // persistent tower claims: 0 one tile, 1 one M tile x all N tiles (default)
-        const int prev = azg::g_tower_group;
-        if (value >= 0 && value <= 1) azg::g_tower_group = value;
-        return prev;
-    }
-    if (key == 22) {  // per-layer 128x64 conv tile-body variant (1 default; 0, 4, 5 A/B, bitwise identical)
-        const int prev = azg::g_conv_var;
-        if (value == 0 || value == 1 || value == 4 || value == 5) azg::g_conv_var = value;
-        return prev;
-    }
-    if (key == 21) {  // per-layer conv: last partial round of the 128x64 launch as 64x64 tiles (1) or not (0)
-        const int prev = azg::g_conv_tail_split;
-        azg::g_conv_tail_split = value ? 1 : 0;
-        return prev;
-    }
-    if (key == 44) {  // train: workgroup cap of the BN apply / BN-backward apply passes (0 = one float4 per thread); bitwise identical
-        const int prev = azg::g_train_apply_grid;
-        if (value >= 0) azg::g_train_apply_grid = value;
-        return prev;
-    }
-    if (key == 24) {  // train: BN finalize fused into the producing conv's last workgroup (1, default) or separate (0; two-stream backward); bitwise identical
-        const int prev = azg::g_train_fuse_fin;
-        if (value == 0 || value == 1) azg::g_train_fuse_fin = value;
-        return prev;
-    }
-    if (key == 27) {  // train wgrad split-K count (0 automatic; 8..64, multiple of 8); bitwise NOT identical across values
-        const int prev = azg::g_wgrad_splits;
-        if (value == 0 || (value >= 8 && value <= 64 && value % 8 == 0)) azg::g_wgrad_splits = value;
-        return prev;
-    }
-    if (key == 23) {  // train: BN applies folded into the next conv's halo staging (1, default) or separate passes (0); bitwise identical
-        const int prev = azg::g_train_fuse_apply;
-        if (value == 0 || value == 1) azg::g_train_fuse_apply = value;
-        return prev;
-    }
-    if (key == 11) {  // stem ablation mask (timing studies only)
-        const int prev = azg::g_stem_ablation;
-#ifdef AZG_AB_STUDIES   // timing studies only: the product library ignores it
-        azg::g_stem_ablation = value;
-#endif
-        return prev;
-    }
-    if (key == 9) {   // stem kernel: 1 fp32 MFMA (default), 0 VALU reference
-        const int prev = azg::g_stem_variant;
-        if (value == 0 || value == 1) azg::g_stem_variant = value;
-        return prev;
-    }
-    if (key == 10) {  // persistent-tower tile body variant (A/B studies, bitwise identical)
-        const int prev = azg::g_tower_var;
-#ifdef AZG_AB_STUDIES
-        if ((value >= 0 && value <= 8) || value == 12 || value == 13 || value == 14 || value == 15 || value == 16) azg::g_tower_var = value;
-#else
-        if (value == 0) azg::g_tower_var = value;
-#endif
-        return prev;
-    }
-    if (key == 8) {   // persistent-tower ablation mask (timing studies only)
-        const int prev = azg::g_tower_ablation;
-#ifdef AZG_AB_STUDIES   // timing studies only: the product library ignores it
-        azg::g_tower_ablation = value;
-#endif
-        return prev;
-    }
-    if (key == 7) {   // ablation tile shape (5 or 8)
-        const int prev = azg::g_ablation_shape;
-#ifdef AZG_AB_STUDIES   // timing studies only: the product library ignores it
-        azg::g_ablation_shape = value;
-#endif
-        return prev;
-    }
-    if (key == 5) {   // persistent residual tower on/off
-        const int prev = azg::g_tower_mode;
-        azg::g_tower_mode = value;
-        return prev;
-    }
-    if (key == 6) {   // persistent tower tile shape
-        const int prev = azg::g_tower_shape;
-        if (value == 5 || value == 8 || value == 10 || value == 12 || value == 13 || value == 14) azg::g_tower_shape = value;
-#ifdef AZG_AB_STUDIES
-        if (value == 9) azg::g_tower_shape = value;
-#endif
-        return prev;
-    }
-    if (key == 4) {   // conv kernel variant (1 halo-staged, 0 per-chunk staging; timing studies)
-        const int prev = azg::g_conv_variant;
-#ifdef AZG_AB_STUDIES   // timing studies only: the product library ignores it
-        azg::g_conv_variant = value;
-#endif
-        return prev;
-    }
-    if (key == 15) {  // query: 1 if built with the A/B study variants (make study)
-#ifdef AZG_AB_STUDIES
-        return 1;
-#else
-        return 0;
-#endif
-    }
-    if (key == 2) {   // query: tuned shape for (C, M) packed as value = M*1024 + C
-        return azg::conv_tuned_shape(value & 1023, value >> 10);
-    }
-    return -1;
-}

@@ -43,18 +43,36 @@ hipError_t launch_conv3x3_train(int C, int epi, int xe, const float* in, const f
                                 float* out, int M, const EpiX& ex, hipStream_t st, const ProX* px = nullptr,
                                 const FinX* fx = nullptr, const float* oscale = nullptr, unsigned* h3ovf = nullptr,
                                 const unsigned* dmax = nullptr);
-extern int g_train_dgrad_h3;   // key 50: the train step's dgrad convs in split-fp16 (2: four products, 1: three, 0: fp32)
-extern int g_train_h3;   // key 49: the train step's forward convs in split-fp16 (1) or fp32 MFMA (0)
+// process-wide tuning variables (azg_pv_set_tuning, pv_tuning.hip: one table row per key)
+extern int g_conv_shape_override;   // pv_conv.hip
+extern int g_conv_autotune;
+extern int g_conv_ablation;
+extern int g_conv_variant;
+extern int g_ablation_shape;
+extern int g_conv_tail_split;
+extern int g_conv_var;
+extern int g_stem_variant;
+extern int g_stem_ablation;
 extern int g_tower_mode;
-extern int g_conv_shape_override;
-extern int g_tower_shape;
+extern int g_train_h3;         // the train step's forward convs in split-fp16 (2: four products, 1: three, 0: fp32)
+extern int g_train_dgrad_h3;   // the train step's dgrad convs, likewise
+extern int g_tower_shape;      // pv_tower.hip
 extern int g_tower_ablation;
 extern int g_tower_var;
-extern int g_train_fuse_apply;
+extern int g_tower_group;
+extern int g_tower_h3;         // eval residual-conv arithmetic: 2 / 1 split-fp16 (16x16x32 / 32x32x16), 0 fp32
+extern int g_h3_tower_var;
+extern unsigned g_tower_wait_us;
+extern int g_tower_coh;        // study build only
+extern int g_board_abl;        // pv_board.hip (read by the study build only)
+extern int g_board16_split;    // pv_board16.hip
+extern int g_tower_breaker_s;  // pv_capi.hip: seconds of per-layer convs after a recovered launch
+extern int g_train_fuse_apply; // pv_train.hip
 extern int g_train_fuse_fin;
 extern int g_train_apply_grid;
-extern int g_wgrad_splits;
+extern int g_wgrad_splits;     // pv_wgrad.hip
 extern int g_wgrad_variant;
+int conv_tuned_shape(int C, int M);   // QUERY_CONV_SHAPE: the autotuned tile shape, -1 if not tuned yet
 hipError_t launch_stem_stats(int C, const float* x, const float* ws, float* out, int B, float* pa, float* pb,
                              hipStream_t st);
 constexpr int kTowerMaxBlocks = 32;
@@ -72,7 +90,6 @@ constexpr int kTowerDiagWords = 64;           // device wait record (pv_tower.hi
 constexpr unsigned kTowerWaitUs = 100000u;    // default awake-time bound of one dependency wait: 100 ms
                                               // (longest legitimate wait measured: 7.3 ms, two processes
                                               // sharing the GPU; 0.26 ms alone -- DESIGN.md section 7)
-extern int g_tower_breaker_s;                 // key 18: seconds of per-layer convs after a recovered launch
 struct TowerSync {
     unsigned* sync;   // tower_sync_bytes: memset per launch
     unsigned* ring;   // host-mapped ring (device alias)
@@ -97,7 +114,6 @@ struct Board16Split {
     unsigned* ring;    // timed-out launch ring (device alias), azg_pv_recover
     unsigned* diag;    // the tower wait record
 };
-extern int g_board16_split;   // key 52
 int board16_grid();           // workgroups of a one-per-CU board16 launch (0: init failed)
 int board16_split_max();      // largest batch the split form takes (key 52, CUs / 3, kB16SplitCap)
 constexpr int kB16SplitCap = 85;                        // 3 x 85 workgroups <= 256 CUs
@@ -111,11 +127,6 @@ hipError_t launch_board16_tower(int NB, const float* wp16, const float* scale16,
 
 // the heads' 1x1 projection epilogue: folded eval BN + ReLU (heads_project and the board16 tower)
 __device__ __forceinline__ float head_bn_relu(float d, float s, float h) { return fmaxf(d * s + h, 0.f); }
-extern unsigned g_tower_wait_us;
-extern int g_tower_group;
-#ifdef AZG_AB_STUDIES
-extern int g_tower_coh;
-#endif
 hipError_t launch_stem(int C, int epi, const float* x, const float* ws, const float* scale,
                        const float* shift, float* out, int B, hipStream_t st, const int8_t* boards = nullptr,
                        const int8_t* players = nullptr, const int8_t* syms = nullptr, int symmode = SYM_NONE);
@@ -150,10 +161,30 @@ hipError_t launch_pack_h3(const float* params, const int64_t* offs, int nl, int 
                           const float* scale, int* exps, void* wp16, float* scale16, float* inv, hipStream_t st);
 hipError_t launch_pack_h3_dgrad(const float* params, const int64_t* offs, int nl, int C, const int* exps, void* wd16,
                                 hipStream_t st);
-extern int g_tower_h3;
-extern int g_h3_tower_var;
 hipError_t launch_fold_bn(const float* params, const float* stats, const void* desc, int nlayers,
                           float* scale, float* shift, hipStream_t st);
+
+// What one eval forward reads and writes.  `batch` counts BOARDS, here and in every host
+// function that takes an EvalCall; the kernel launchers' B / M count IMAGES (images():
+// 8 per board under SYM_MEAN8, the stem reading each board through its symmetries), and so
+// do the workspace size and the profile's board counts.
+struct EvalCall {
+    const float* x = nullptr;          // float planes [batch][3][15][15], or
+    const int8_t* boards = nullptr;    // int8 boards and players to move (x null)
+    const int8_t* players = nullptr;
+    const int8_t* syms = nullptr;      // SYM_EACH: one symmetry per board
+    int symmode = SYM_NONE;
+    int batch = 0;
+    float *probs = nullptr, *values = nullptr;
+    float *logits = nullptr, *priors = nullptr;   // optional
+    int images() const { return symmode == SYM_MEAN8 ? 8 * batch : batch; }
+};
+// azg_pv_recover's recompute of a posted launch
+struct EvalOpts {
+    bool per_layer = false;    // per-layer convs (no cross-workgroup waits); posts no new launch
+    bool fp32_only = false;    // fp32 MFMA although split-fp16 is selected
+    unsigned guard_seq = 0;    // split-fp16 recompute: a range overflow posts this number
+};
 
 }  // namespace azg
 
@@ -172,6 +203,7 @@ struct azg_pv {
     std::vector<azg::BnDesc> bn_desc;
     int bn_stem = 0, bn_pol = 0, bn_val = 0;
     std::vector<azg::BlockBn> bn_blk;
+    std::vector<void*> dev_allocs;   // every handle-lifetime hipMalloc (azg_pv_destroy frees them)
     void* bn_desc_dev = nullptr;
     int64_t* conv_off_dev = nullptr;   // flat-param offset of each 3x3 conv weight (2*NB, block order)
 
@@ -199,6 +231,7 @@ struct azg_pv {
     int* h3exp = nullptr;
     float* h3inv = nullptr;   // [2 NB][C]: 2^-e of each conv (train forward, raw outputs)
     int* conv_bn_off_dev = nullptr;
+    std::vector<int> conv_bn_off;   // folded-BN offset of each residual conv (2*NB; build_layout)
     bool h3_dirty = true;
     unsigned h3_gen = 0;   // + 1 per split-fp16 re-pack (the train step's dgrad pack follows it)
 
@@ -222,14 +255,8 @@ struct azg_pv {
     // what each posted launch read and wrote, by seq % kTowerRing (azg_pv_recover re-runs it)
     struct LaunchRec {
         unsigned seq = 0;
-        const float* x = nullptr;
-        const int8_t* boards = nullptr;
-        const int8_t* players = nullptr;
-        int batch = 0;
         bool h3 = false;
-        float *probs = nullptr, *values = nullptr, *logits = nullptr, *priors = nullptr;
-        const int8_t* syms = nullptr;   // azg_pv_forward_boards_sym: the symmetries and the mode
-        int symmode = azg::SYM_NONE;    // (batch counts boards, not images)
+        azg::EvalCall call;
     };
     std::vector<LaunchRec> launches;
     uint32_t recovered = 0;           // launches recomputed per layer
@@ -259,14 +286,11 @@ int32_t set_error(const char* what, hipError_t e);
 void build_layout(azg_pv* h);
 void free_workspace(azg_pv* h);
 void free_train_workspace(azg_pv* h);
-int32_t ensure_eval_workspace(azg_pv* h, int batch, hipStream_t st);
+int32_t ensure_eval_workspace(azg_pv* h, int images, hipStream_t st);
 int32_t repack(azg_pv* h, hipStream_t st, float* dgrad_dst = nullptr, int part = 0);   // dgrad_dst: also pack dgrad weights
 int32_t ensure_h3(azg_pv* h, hipStream_t st);   // split-fp16 packs of the current parameters
 int prof_begin(azg_pv* h, int cls, hipStream_t st, int64_t boards = 0);   // returns pair index or -1
 hipError_t prof_harvest(azg_pv* h);
 void prof_end(azg_pv* h, int pair, hipStream_t st);
-int32_t forward_eval(azg_pv* h, const float* x, int batch, float* probs, float* values, float* logits,
-                     hipStream_t st, const int8_t* boards, const int8_t* players, float* priors,
-                     bool per_layer = false, bool fp32_only = false, unsigned guard_seq = 0,
-                     const int8_t* syms = nullptr, int symmode = SYM_NONE);
+int32_t forward_eval(azg_pv* h, const EvalCall& c, hipStream_t st, const EvalOpts& o = {});
 }  // namespace azg

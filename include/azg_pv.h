@@ -209,91 +209,137 @@ int32_t azg_pv_profile_read(azg_pv* h, double* ms, int64_t* launches);
  * BOARD launch counts its batch once for all 2*blocks convs. */
 int32_t azg_pv_profile_boards(const azg_pv* h, int64_t* boards);
 
-/* Process-wide tuning knobs (benchmarks / A-B tests).  Returns the previous value.
- *   key 0: force the 3x3-conv tile shape index (-1 = automatic);
- *   key 1: conv autotuning on/off (default on: the first launch for a (C, M) times
- *          every tile shape on the real operands and caches the fastest; shapes give
- *          bitwise-identical results, so this never changes numerics);
- *   key 2: query the tuned shape for value = M*1024 + C (-1 if not tuned yet);
- *   key 4: conv kernel variant (1 halo-staged, default; 0 per-chunk staging, timing only);
- *   key 5: eval residual tower: 0 one launch per conv, 1 one persistent launch
- *          (shape from key 6), 2 (default) chosen per (C, blocks, batch bucket) by
- *          timing every variant on first use -- all bitwise identical;
- *   key 6: persistent-tower tile shape for key 5 = 1 (8: 128x64 / 8 waves, default;
- *          5: 64x64 / 4 waves; 10: 128x128 / 16 waves, one workgroup per CU, C = 128, fp32
- *          only; 12: h3_tile 128x128 / 4 waves of 64x64, split-fp16 only; 13: the
- *          board-resident tower (pv_board.hip: one board per 16-wave workgroup, its
- *          activations in LDS through every conv), split-fp16 and C = 128 only -- a shape
- *          the current arithmetic lacks runs as 8); with key 19 = 2 at C = 128 keys 5 / 6
- *          do not apply (one form: the 16x16x32 board tower);
- *   keys 3, 7, 8: timing-only ablation switches (results invalid while set);
- *   key 10: tile-body variant of the C=128 128x64 persistent tower (0 = default;
- *          1..5 = swizzle / prefetch / LDS-DMA staging variants for A/B timing, all
- *          bitwise identical to 0);
- *   key 9: stem kernel (1 = fp32 MFMA, default; 0 = VALU reference, bitwise equal);
- *   key 11: stem ablation mask (timing only, results invalid while set);
- *   key 17: persistent-tower claim granularity (1 = one M tile with all its N
- *          tiles, run back to back by the claiming workgroup, default: the second
- *          tile's halo rows hit the XCD's L2, +2 % at B = 512 and 4096, measured;
- *          0 = one 128x64 tile per claim); bitwise identical results;
- *   key 21: per-layer 128x64 conv: the last partial round of workgroups runs as a
- *          second launch of 64x64 tiles (1, default) or not (0); bitwise identical;
- *   key 22: per-layer 128x64 conv tile body (1 = halo rows keyed on the board
- *          position, conflict-free fragment reads, default; 0 = row-keyed; 4 / 5 =
- *          LDS-DMA staging); bitwise identical;
- *   key 23: train forward BN apply + ReLU (+ residual) folded into the next conv's
- *          halo staging (1, default; C <= 128 only: at C = 256 the prologue spills
- *          and the separate passes are faster) or separate bn_apply passes (0);
- *          bitwise identical;
- *   key 24: train BN finalize run by the last workgroup of the conv producing the
- *          layer's partials (1, default) or by separate finalize kernels (0); one
- *          shared fp64 reduction order, bitwise identical;
- *   key 27: train conv weight-grad pixel splits (0 = automatic, default; 8..64, a
- *          multiple of 8); bitwise identical only at a fixed value;
- *   key 44: train BN apply / BN-backward apply passes: workgroup cap of their
- *          grid-stride launch (0 = four float4 per thread, default); bitwise identical;
- *   key 31: study build only: the 64x64 / 128x64 towers with sc1 dependent loads
- *          and no acquire (two or more workgroups per CU: outside the microarch
- *          guide's measured envelope; the product uses the acquire there and the
- *          sc1 form only for the one-workgroup-per-CU 16-wave tile); returns 0 in
- *          the product library;
- *   key 14: persistent-tower dependency wait bound in microseconds of the waiting
- *          wave's awake time (default 100000 = 100 ms; -1 restores it; 0 makes every
- *          dependency wait time out at once, exercising the recovery path);
- *   key 19: eval residual-conv arithmetic: 2 (default) and 1 split-fp16 -- every fp32
- *          operand x is split into hi = fp16(x), lo = fp16(x - hi) and a product is lo*hi +
- *          hi*lo + hi*hi by fp16 MFMAs with fp32 accumulation (weights scaled by a per-layer
- *          power of two, undone in the BN scale; error ~2^-22 per product, the fp32 MFMA
- *          chain's order of magnitude); 1 sums 16 channels per
- *          v_mfma_f32_32x32x16_f16 (per-layer launches, tile towers, the 32x32 board
- *          tower), 2 at C = 128 sums 32 per v_mfma_f32_16x16x32_f16 in the 16x16x32 board
- *          tower (pv_board16.hip), the one form of that arithmetic (C = 256: as 1); 0 fp32
- *          MFMA.  Every eval path (tower, per-layer, recompute) uses the selected
- *          arithmetic, so within it the forms are bitwise equal and the forward is
- *          batch-independent.  An activation at or above fp16's
- *          range (65520 rounds to inf) makes its products non-finite: the epilogue posts
- *          the launch and azg_pv_recover recomputes it with fp32 MFMA.  The train step
- *          always uses fp32 MFMA;
- *   key 52: key 19 = 2 at C = 128: the largest batch whose boards each run over three 8-wave
- *          workgroups (pixel thirds) that exchange their conv outputs' 16 boundary rows through
- *          L2 (default 85: 3 x 85 workgroups fit 256 CUs; 0 never) -- bitwise the one-workgroup
- *          tower, about 2/3 of its latency; a timed-out exchange wait (key 14) posts the launch
- *          (azg_pv_recover reruns it one workgroup per board);
- *   key 20: the split-fp16 tower's tile body (1 = halo rows keyed on the board position,
- *          conflict-free fragment reads, default; 0 = row-keyed); bitwise identical;
- *   key 49: train-step forward convs: 2 (default) split-fp16 with all four hi / lo products
- *          (~2^-33 per product: the two-step goldens hold), 1 three products, 0 fp32 MFMA;
- *          the dgrad convs and weight grads stay fp32; a staged activation beyond fp16's
- *          range sets the step's skip word (azg_pv_bind): the step does not commit and the
- *          caller redoes it in fp32 (azg_pv_train_fp32_once);
- *   key 48: train weight-grad tile (1 = padded-row table, buffer LDS-DMA, slabs in the
- *          MFMA layout, default; 0 = round-4 form); bitwise identical;
- *   key 18: seconds a handle runs per-layer convs after azg_pv_recover recomputed one
- *          of its tower launches (default 30; 0 disables the breaker).  A timed-out
- *          wait means parts of the dispatch were suspended while others ran (the GPU is
- *          shared with another process); per-layer launches have no
- *          cross-workgroup waits.
- *   Every call returns the previous value. */
+/* Keys of azg_pv_set_tuning: process-wide tuning knobs (benchmarks / A-B tests).  The
+ * numbers are frozen: benchmarks and scripts pass them as integers. */
+enum azg_pv_tuning_key {
+    /* force the 3x3-conv tile shape index (-1 = automatic) */
+    AZG_PV_TUNE_CONV_SHAPE = 0,
+    /* conv autotuning on/off (default on: the first launch for a (C, M) times every tile
+     * shape on the real operands and caches the fastest; shapes give bitwise-identical
+     * results, so this never changes numerics) */
+    AZG_PV_TUNE_CONV_AUTOTUNE = 1,
+    /* query the tuned shape for value = M*1024 + C (-1 if not tuned yet) */
+    AZG_PV_TUNE_QUERY_CONV_SHAPE = 2,
+    /* timing-only ablation mask of the per-layer conv (results invalid while set);
+     * study build only: the product library ignores a set */
+    AZG_PV_TUNE_CONV_ABLATION = 3,
+    /* conv kernel variant (1 halo-staged, default; 0 per-chunk staging, timing only);
+     * study build only: the product library ignores a set */
+    AZG_PV_TUNE_CONV_STAGING = 4,
+    /* eval residual tower: 0 one launch per conv, 1 one persistent launch (shape from
+     * TOWER_SHAPE), 2 (default) chosen per (C, blocks, batch bucket) by timing every
+     * variant on first use -- all bitwise identical */
+    AZG_PV_TUNE_TOWER_MODE = 5,
+    /* persistent-tower tile shape for TOWER_MODE = 1 (8: 128x64 / 8 waves, default;
+     * 5: 64x64 / 4 waves; 10: 128x128 / 16 waves, one workgroup per CU, C = 128, fp32
+     * only; 12: h3_tile 128x128 / 4 waves of 64x64, split-fp16 only; 13: the
+     * board-resident tower (pv_board.hip: one board per 16-wave workgroup, its
+     * activations in LDS through every conv), split-fp16 and C = 128 only -- a shape
+     * the current arithmetic lacks runs as 8); with EVAL_ARITH = 2 at C = 128
+     * TOWER_MODE / TOWER_SHAPE do not apply (one form: the 16x16x32 board tower) */
+    AZG_PV_TUNE_TOWER_SHAPE = 6,
+    /* tile shape (5 or 8) the timing-only ablations run; study build only */
+    AZG_PV_TUNE_ABLATION_SHAPE = 7,
+    /* timing-only ablation mask of the persistent tower (results invalid while set);
+     * study build only */
+    AZG_PV_TUNE_TOWER_ABLATION = 8,
+    /* stem kernel (1 = fp32 MFMA, default; 0 = VALU reference, bitwise equal) */
+    AZG_PV_TUNE_STEM_KERNEL = 9,
+    /* tile-body variant of the C=128 128x64 persistent tower (0 = default; the study
+     * build also takes 1..8 and 12..16 = swizzle / prefetch / LDS-DMA staging variants
+     * for A/B timing, all bitwise identical to 0) */
+    AZG_PV_TUNE_TOWER_BODY = 10,
+    /* stem ablation mask (timing only, results invalid while set); study build only */
+    AZG_PV_TUNE_STEM_ABLATION = 11,
+    /* persistent-tower dependency wait bound in microseconds of the waiting wave's
+     * awake time (default 100000 = 100 ms; -1 restores it; 0 makes every dependency
+     * wait time out at once, exercising the recovery path) */
+    AZG_PV_TUNE_TOWER_WAIT_US = 14,
+    /* query: 1 if the library was built with the A/B study variants (make study) */
+    AZG_PV_TUNE_QUERY_STUDY_BUILD = 15,
+    /* persistent-tower claim granularity (1 = one M tile with all its N tiles, run
+     * back to back by the claiming workgroup, default: the second tile's halo rows hit
+     * the XCD's L2, +2 % at B = 512 and 4096, measured; 0 = one 128x64 tile per
+     * claim); bitwise identical results */
+    AZG_PV_TUNE_TOWER_CLAIM = 17,
+    /* seconds a handle runs per-layer convs after azg_pv_recover recomputed one of its
+     * tower launches (default 30; 0 disables the breaker).  A timed-out wait means
+     * parts of the dispatch were suspended while others ran (the GPU is shared with
+     * another process); per-layer launches have no
+     * cross-workgroup waits */
+    AZG_PV_TUNE_BREAKER_SECONDS = 18,
+    /* eval residual-conv arithmetic: 2 (default) and 1 split-fp16 -- every fp32 operand
+     * x is split into hi = fp16(x), lo = fp16(x - hi) and a product is lo*hi + hi*lo +
+     * hi*hi by fp16 MFMAs with fp32 accumulation (weights scaled by a per-layer power
+     * of two, undone in the BN scale; error ~2^-22 per product, the fp32 MFMA chain's
+     * order of magnitude); 1 sums 16 channels per
+     * v_mfma_f32_32x32x16_f16 (per-layer launches, tile towers, the 32x32 board
+     * tower), 2 at C = 128 sums 32 per v_mfma_f32_16x16x32_f16 in the 16x16x32 board
+     * tower (pv_board16.hip), the one form of that arithmetic (C = 256: as 1); 0 fp32
+     * MFMA.  Every eval path (tower, per-layer, recompute) uses the selected
+     * arithmetic, so within it the forms are bitwise equal and the forward is
+     * batch-independent.  An activation at or above fp16's range (65520 rounds to inf)
+     * makes its products non-finite: the epilogue posts the launch and azg_pv_recover
+     * recomputes it with fp32 MFMA */
+    AZG_PV_TUNE_EVAL_ARITH = 19,
+    /* the split-fp16 tower's tile body (1 = halo rows keyed on the board position,
+     * conflict-free fragment reads, default; 0 = row-keyed); bitwise identical */
+    AZG_PV_TUNE_H3_TOWER_BODY = 20,
+    /* per-layer 128x64 conv: the last partial round of workgroups runs as a second
+     * launch of 64x64 tiles (1, default) or not (0); bitwise identical */
+    AZG_PV_TUNE_CONV_TAIL_SPLIT = 21,
+    /* per-layer 128x64 conv tile body (1 = halo rows keyed on the board position,
+     * conflict-free fragment reads, default; 0 = row-keyed; 4 / 5 = LDS-DMA staging);
+     * bitwise identical */
+    AZG_PV_TUNE_CONV_BODY = 22,
+    /* train forward BN apply + ReLU (+ residual) folded into the next conv's halo
+     * staging (1, default; C <= 128 only: at C = 256 the prologue spills and the
+     * separate passes are faster) or separate bn_apply passes (0); bitwise identical */
+    AZG_PV_TUNE_TRAIN_FUSE_APPLY = 23,
+    /* train BN finalize run by the last workgroup of the conv producing the layer's
+     * partials (1, default) or by separate finalize kernels (0); one shared fp64
+     * reduction order, bitwise identical */
+    AZG_PV_TUNE_TRAIN_FUSE_FINALIZE = 24,
+    /* train conv weight-grad pixel splits (0 = automatic, default; 8..64, a multiple
+     * of 8); bitwise identical only at a fixed value */
+    AZG_PV_TUNE_WGRAD_SPLITS = 27,
+    /* study build only: the 64x64 / 128x64 towers with sc1 dependent loads and no
+     * acquire (two or more workgroups per CU: outside the microarch guide's measured
+     * envelope; the product uses the acquire there and the sc1 form only for the
+     * one-workgroup-per-CU 16-wave tile); returns 0 in the product library */
+    AZG_PV_TUNE_TOWER_SC1_LOADS = 31,
+    /* train BN apply / BN-backward apply passes: workgroup cap of their grid-stride
+     * launch (0 = four float4 per thread, default); bitwise identical */
+    AZG_PV_TUNE_TRAIN_APPLY_GRID = 44,
+    /* train weight-grad tile (1 = padded-row table, buffer LDS-DMA, slabs in the MFMA
+     * layout, default; 0 = round-4 form); bitwise identical */
+    AZG_PV_TUNE_WGRAD_TILE = 48,
+    /* train-step forward convs: 2 (default) split-fp16 with all four hi / lo products
+     * (~2^-33 per product: the two-step goldens hold), 1 three products, 0 fp32 MFMA;
+     * the weight grads stay fp32; a staged activation beyond fp16's range sets the
+     * step's skip word (azg_pv_bind): the step does not commit and the caller redoes
+     * it in fp32 (azg_pv_train_fp32_once) */
+    AZG_PV_TUNE_TRAIN_ARITH = 49,
+    /* train-step dgrad convs: 0 (default) fp32 MFMA, 1 split-fp16 with three products,
+     * 2 with four (inputs scaled by a power of two from their maximum); measured
+     * slower and below the two-step goldens */
+    AZG_PV_TUNE_TRAIN_DGRAD_ARITH = 50,
+    /* timing ablations of the board towers (1 no DMA wait, 2 no barrier, 4 no
+     * epilogue; results invalid while set); study build only: the product library
+     * does not know the key (-1) */
+    AZG_PV_TUNE_BOARD_ABLATION = 51,
+    /* EVAL_ARITH = 2 at C = 128: the largest batch whose boards each run over three
+     * 8-wave workgroups (pixel thirds) that exchange their conv outputs' 16 boundary
+     * rows through L2 (default 85: 3 x 85 workgroups fit 256 CUs; 0 never) -- bitwise
+     * the one-workgroup tower, about 2/3 of its latency; a timed-out exchange wait
+     * (TOWER_WAIT_US) posts the launch (azg_pv_recover reruns it one workgroup per
+     * board) */
+    AZG_PV_TUNE_BOARD16_SPLIT_MAX = 52
+};
+
+/* Sets the knob `key` (an azg_pv_tuning_key) and returns its previous value; a value the
+ * key does not accept leaves it unchanged.  The two queries return their answer; an
+ * unknown key returns -1. */
 int32_t azg_pv_set_tuning(int32_t key, int32_t value);
 
 /* Persistent-tower dependency waits (pv_tower.hip).  A tile of the one-launch eval

@@ -26,6 +26,7 @@ import torch
 import torch.multiprocessing as mp
 
 from conftest import PKG, REPO, has_gpu
+from _native import TUNE
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
 
@@ -294,11 +295,11 @@ def _ovf_worker(rank, world, port, out_dir):
             m.net.bn.weight.copy_(gamma.to(m.engine.device))
         m.engine.mark_dirty()
         m.grad_hook = D.grad_hook()
-        prev = lib.azg_pv_set_tuning(49, key49)
+        prev = lib.azg_pv_set_tuning(TUNE.TRAIN_ARITH, key49)
         try:
             losses = m.train_batch(x, pi, z)
         finally:
-            lib.azg_pv_set_tuning(49, prev)
+            lib.azg_pv_set_tuning(TUNE.TRAIN_ARITH, prev)
         D.sync_bn_stats(m)   # running stats are rank-local until averaged (train.py does it per iteration)
         out.update({f"{tag}_{k}": v for k, v in _state(m).items()})
         out[f"{tag}_losses"] = np.array([losses[k] for k in ("policy_loss", "value_loss", "total_loss")])

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import golden_state, has_gpu, load_golden
+from _native import TUNE
 from oracle.boards import encode_batch, synth_positions, valid_mask
 from oracle.ref_net import RefModel, load_numpy_state, state_to_numpy
 
@@ -112,17 +113,17 @@ def test_split_forward_on_trained_weights_matches_oracle32(blocks, ch, seed, B, 
     load_numpy_state(ref.net, st)
     b, p = synth_positions(B, seed=B + 7 * ch)
     x = encode_batch(b, p)
-    prev19 = lib.azg_pv_set_tuning(19, cls)
-    prev5, prev6 = lib.azg_pv_set_tuning(5, 1), lib.azg_pv_set_tuning(6, shape)
+    prev19 = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, cls)
+    prev5, prev6 = lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 1), lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, shape)
     try:
         m.engine.profile_enable(True)
         probs, values = m.predict(x)
         ran = m.engine.profile_read()
         m.engine.profile_enable(False)
     finally:
-        lib.azg_pv_set_tuning(5, prev5)
-        lib.azg_pv_set_tuning(6, prev6)
-        lib.azg_pv_set_tuning(19, prev19)
+        lib.azg_pv_set_tuning(TUNE.TOWER_MODE, prev5)
+        lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, prev6)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev19)
     assert {14: "board16", 12: "tower16"}.get(shape, "tower") in ran, ran
     rp, rv = ref.predict(x)
     n64 = min(B, 256)
@@ -166,7 +167,7 @@ def test_forward_is_batch_independent(blocks, ch, cls, n):
     m = make_model(blocks, ch)
     b, p = synth_positions(n, seed=3)
     x = encode_batch(b, p)
-    prev = lib.azg_pv_set_tuning(19, cls)
+    prev = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, cls)
     try:
         probs, values = m.predict(x)
         for i in (0, 63, 64, 129, n - 1):
@@ -178,7 +179,7 @@ def test_forward_is_batch_independent(blocks, ch, cls, n):
         ps, vs = m.predict(x[37:37 + 300])
         assert np.array_equal(ps, probs[37:337]) and np.array_equal(vs, values[37:337])
     finally:
-        lib.azg_pv_set_tuning(19, prev)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev)
 
 
 def test_empty_and_full_boards():
@@ -286,31 +287,31 @@ def test_persistent_tower_bitwise_equals_per_layer_launches(blocks, ch, batches)
     m = make_model(blocks, ch, state_to_numpy(ref.net))
     eng = m.engine
     stream = torch.cuda.current_stream().cuda_stream
-    prev_mode = lib.azg_pv_set_tuning(5, 1)
-    prev_shape = lib.azg_pv_set_tuning(6, 8)
-    prev_h3 = lib.azg_pv_set_tuning(19, 1)
+    prev_mode = lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 1)
+    prev_shape = lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, 8)
+    prev_h3 = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 1)
     try:
         for h3, B in [(h, b) for h in (1, 0) for b in batches]:
-            lib.azg_pv_set_tuning(19, h3)
+            lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, h3)
             x = torch.from_numpy(synth_encoded(B, seed=B)).cuda()
-            lib.azg_pv_set_tuning(5, 0)
+            lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 0)
             p0, v0, l0 = eng.forward(x, want_logits=True)
-            lib.azg_pv_set_tuning(5, 1)
+            lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 1)
             # 12: h3_tile, 13: the board-resident tower (split-fp16 only; 13 needs C = 128)
             for shape in ((5, 8, 10, 12, 13) if ch == 128 else (5, 8, 12)):
-                lib.azg_pv_set_tuning(6, shape)
+                lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, shape)
                 for group in (0, 1):   # claims (key 17): one tile, one M tile
-                    prev_group = lib.azg_pv_set_tuning(17, group)
+                    prev_group = lib.azg_pv_set_tuning(TUNE.TOWER_CLAIM, group)
                     for rep in range(3):
                         p1, v1, l1 = eng.forward(x, want_logits=True)
                         assert lib.azg_pv_tower_status(eng.h, stream) == 0
                         assert torch.equal(l0, l1), (h3, B, shape, group, rep, float((l0 - l1).abs().max()))
                         assert torch.equal(p0, p1) and torch.equal(v0, v1), (h3, B, shape, group, rep)
-                    lib.azg_pv_set_tuning(17, prev_group)
+                    lib.azg_pv_set_tuning(TUNE.TOWER_CLAIM, prev_group)
     finally:
-        lib.azg_pv_set_tuning(19, prev_h3)
-        lib.azg_pv_set_tuning(6, prev_shape)
-        lib.azg_pv_set_tuning(5, prev_mode)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev_h3)
+        lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, prev_shape)
+        lib.azg_pv_set_tuning(TUNE.TOWER_MODE, prev_mode)
 
 
 @pytest.mark.parametrize("blocks,ch,B", [(6, 128, 300), (6, 128, 2048), (6, 128, 2600), (2, 256, 600), (2, 64, 2100)])
@@ -329,23 +330,23 @@ def test_per_layer_variants_bitwise(blocks, ch, B):
     m = make_model(blocks, ch, state_to_numpy(ref.net))
     eng = m.engine
     x = torch.from_numpy(synth_encoded(B, seed=B + 1)).cuda()
-    prev = {k: lib.azg_pv_set_tuning(k, v) for k, v in ((5, 0), (0, 5), (19, 0))}
-    prev[22] = lib.azg_pv_set_tuning(22, 1)
-    prev[21] = lib.azg_pv_set_tuning(21, 1)
+    prev = {k: lib.azg_pv_set_tuning(k, v) for k, v in ((TUNE.TOWER_MODE, 0), (TUNE.CONV_SHAPE, 5), (TUNE.EVAL_ARITH, 0))}
+    prev[TUNE.CONV_BODY] = lib.azg_pv_set_tuning(TUNE.CONV_BODY, 1)
+    prev[TUNE.CONV_TAIL_SPLIT] = lib.azg_pv_set_tuning(TUNE.CONV_TAIL_SPLIT, 1)
     try:
         _, _, l0 = eng.forward(x, want_logits=True)
-        lib.azg_pv_set_tuning(0, 8)
+        lib.azg_pv_set_tuning(TUNE.CONV_SHAPE, 8)
         for var in (0, 1, 4, 5):
             for split in (0, 1):
-                lib.azg_pv_set_tuning(22, var)
-                lib.azg_pv_set_tuning(21, split)
+                lib.azg_pv_set_tuning(TUNE.CONV_BODY, var)
+                lib.azg_pv_set_tuning(TUNE.CONV_TAIL_SPLIT, split)
                 _, _, l1 = eng.forward(x, want_logits=True)
                 assert torch.equal(l0, l1), (blocks, ch, B, var, split, float((l0 - l1).abs().max()))
         if ch >= 128:
-            lib.azg_pv_set_tuning(19, 1)
-            lib.azg_pv_set_tuning(0, 5)
+            lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 1)
+            lib.azg_pv_set_tuning(TUNE.CONV_SHAPE, 5)
             _, _, h5 = eng.forward(x, want_logits=True)
-            lib.azg_pv_set_tuning(0, 8)
+            lib.azg_pv_set_tuning(TUNE.CONV_SHAPE, 8)
             _, _, h8 = eng.forward(x, want_logits=True)
             assert torch.equal(h5, h8), ("h3", blocks, ch, B, float((h5 - h8).abs().max()))
             assert float((h5 - l0).abs().max()) < 1e-4
@@ -365,17 +366,17 @@ def test_persistent_tower_under_concurrent_load():
     m2 = make_model(6, 128, seed=5)
     x1 = torch.from_numpy(synth_encoded(512, seed=11)).cuda()
     x2 = torch.from_numpy(synth_encoded(1024, seed=12)).cuda()
-    prev_mode = lib.azg_pv_set_tuning(5, 0)
-    prev_shape = lib.azg_pv_set_tuning(6, 8)
-    prev_h3 = lib.azg_pv_set_tuning(19, 1)   # the tile towers' arithmetic (key 19 = 2 has one form)
+    prev_mode = lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 0)
+    prev_shape = lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, 8)
+    prev_h3 = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 1)   # the tile towers' arithmetic (key 19 = 2 has one form)
     try:
         r1 = m1.engine.forward(x1)[0].clone()
         r2 = m2.engine.forward(x2)[0].clone()
-        lib.azg_pv_set_tuning(5, 1)
+        lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 1)
         s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
         torch.cuda.synchronize()
         for shape in (8, 10, 5, 12):
-            lib.azg_pv_set_tuning(6, shape)
+            lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, shape)
             for _ in range(4):
                 with torch.cuda.stream(s1):
                     a = m1.engine.forward(x1)[0]
@@ -384,9 +385,9 @@ def test_persistent_tower_under_concurrent_load():
                 torch.cuda.synchronize()
                 assert torch.equal(a, r1) and torch.equal(b, r2), shape
     finally:
-        lib.azg_pv_set_tuning(19, prev_h3)
-        lib.azg_pv_set_tuning(6, prev_shape)
-        lib.azg_pv_set_tuning(5, prev_mode)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev_h3)
+        lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, prev_shape)
+        lib.azg_pv_set_tuning(TUNE.TOWER_MODE, prev_mode)
 
 
 def test_tower_timeout_is_recovered_bitwise():
@@ -406,10 +407,10 @@ def test_tower_timeout_is_recovered_bitwise():
     x = encode_batch(boards, players)
     bi8, pl8 = np.asarray(boards, np.int8).reshape(512, 225), np.asarray(players, np.int8)
     stream = torch.cuda.current_stream().cuda_stream
-    prev_mode = lib.azg_pv_set_tuning(5, 1)
-    prev_shape = lib.azg_pv_set_tuning(6, 8)
-    prev_breaker = lib.azg_pv_set_tuning(18, 0)     # breaker off: every forward runs the tower
-    prev_h3 = lib.azg_pv_set_tuning(19, 1)          # the tile towers' arithmetic
+    prev_mode = lib.azg_pv_set_tuning(TUNE.TOWER_MODE, 1)
+    prev_shape = lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, 8)
+    prev_breaker = lib.azg_pv_set_tuning(TUNE.BREAKER_SECONDS, 0)     # breaker off: every forward runs the tower
+    prev_h3 = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 1)          # the tile towers' arithmetic
     try:
         p_ok, v_ok = m.predict(x)                    # healthy
         pb_ok, vb_ok = m.predict_boards(bi8, pl8)
@@ -417,7 +418,7 @@ def test_tower_timeout_is_recovered_bitwise():
         eng.tower_diag_clear()
         d0 = eng.tower_diag()
         assert d0["timeouts"] == 0 and d0["recovered"] == 0
-        lib.azg_pv_set_tuning(14, 0)
+        lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, 0)
         r0 = eng.recoveries
         p, v = m.predict(x)
         assert lib.azg_pv_tower_status(eng.h, stream) == 1   # that tower launch timed out ...
@@ -444,7 +445,7 @@ def test_tower_timeout_is_recovered_bitwise():
         assert lib.azg_pv_status(eng.h) == 1
         with pytest.raises(TowerFault, match="timed out"):
             eng.check_status()
-        lib.azg_pv_set_tuning(14, -1)
+        lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, -1)
         assert eng.recover(eng.last_seq())           # still recoverable (buffers intact)
         eng.check_status()
         eng.tower_diag_clear()
@@ -453,10 +454,10 @@ def test_tower_timeout_is_recovered_bitwise():
         assert eng.tower_diag()["timeouts"] == 0
         # the breaker (key 18): after a recovered launch the handle runs per-layer convs
         # (no cross-workgroup waits) until it expires or clear_status closes it
-        lib.azg_pv_set_tuning(18, 30)
-        lib.azg_pv_set_tuning(14, 0)
+        lib.azg_pv_set_tuning(TUNE.BREAKER_SECONDS, 30)
+        lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, 0)
         p, v = m.predict(x)                          # times out, recovered, breaker opens
-        lib.azg_pv_set_tuning(14, -1)
+        lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, -1)
         assert eng.tower_diag()["breaker_trips"] == 1 and np.array_equal(p, p_ok)
         eng.profile_enable(True)
         p, v = m.predict(x)
@@ -470,11 +471,11 @@ def test_tower_timeout_is_recovered_bitwise():
         eng.profile_enable(False)
         assert "tower" in prof                       # the tower again
     finally:
-        lib.azg_pv_set_tuning(14, -1)
-        lib.azg_pv_set_tuning(19, prev_h3)
-        lib.azg_pv_set_tuning(18, prev_breaker)
-        lib.azg_pv_set_tuning(6, prev_shape)
-        lib.azg_pv_set_tuning(5, prev_mode)
+        lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, -1)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev_h3)
+        lib.azg_pv_set_tuning(TUNE.BREAKER_SECONDS, prev_breaker)
+        lib.azg_pv_set_tuning(TUNE.TOWER_SHAPE, prev_shape)
+        lib.azg_pv_set_tuning(TUNE.TOWER_MODE, prev_mode)
         eng.clear_status()
 
 
@@ -491,10 +492,10 @@ def test_mfma_stem_bitwise_equals_valu_stem(blocks, ch, B):
     bi8, pl8 = np.asarray(boards, np.int8), np.asarray(players, np.int8)
     pi, z = synth_targets(B, seed=42)
     outs = []
-    prev = lib.azg_pv_set_tuning(9, 1)
+    prev = lib.azg_pv_set_tuning(TUNE.STEM_KERNEL, 1)
     try:
         for variant in (0, 1):
-            lib.azg_pv_set_tuning(9, variant)
+            lib.azg_pv_set_tuning(TUNE.STEM_KERNEL, variant)
             m = make_model(blocks, ch, seed=9)
             p, v = m.predict(x)
             pb, vb = m.predict_boards(bi8, pl8, masked=False)
@@ -502,7 +503,7 @@ def test_mfma_stem_bitwise_equals_valu_stem(blocks, ch, B):
             p2, v2 = m.predict(x)
             outs.append((p, v, pb, vb, p2, v2))
     finally:
-        lib.azg_pv_set_tuning(9, prev)
+        lib.azg_pv_set_tuning(TUNE.STEM_KERNEL, prev)
     for a, b in zip(outs[0], outs[1]):
         assert np.array_equal(a, b), float(np.abs(a - b).max())
 
@@ -524,12 +525,12 @@ def test_h3_range_guard_recomputes_in_fp32(tower, cls):
     boards, players = synth_positions(256, seed=81)
     x = encode_batch(boards, players)
     bi8, pl8 = np.asarray(boards, np.int8).reshape(256, 225), np.asarray(players, np.int8)
-    prev_mode = lib.azg_pv_set_tuning(5, tower)
-    prev_h3 = lib.azg_pv_set_tuning(19, 0)
+    prev_mode = lib.azg_pv_set_tuning(TUNE.TOWER_MODE, tower)
+    prev_h3 = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 0)
     try:
         p32, v32 = m.predict(x)
         pb32, vb32 = m.predict_boards(bi8, pl8)
-        lib.azg_pv_set_tuning(19, cls)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, cls)
         m.engine.tower_diag_clear()
         p, v = m.predict(x)
         pb, vb = m.predict_boards(bi8, pl8)
@@ -539,8 +540,8 @@ def test_h3_range_guard_recomputes_in_fp32(tower, cls):
         assert np.array_equal(pb, pb32) and np.array_equal(vb, vb32)
         assert lib.azg_pv_status(m.engine.h) == 0
     finally:
-        lib.azg_pv_set_tuning(19, prev_h3)
-        lib.azg_pv_set_tuning(5, prev_mode)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev_h3)
+        lib.azg_pv_set_tuning(TUNE.TOWER_MODE, prev_mode)
 
 
 @pytest.mark.parametrize("blocks,ch,B,cls", [(6, 128, 512, 2), (6, 128, 512, 1), (10, 256, 96, 1)])
@@ -557,13 +558,13 @@ def test_h3_matches_fp32_forward_and_oracle(blocks, ch, B, cls):
     m = make_model(blocks, ch, state_to_numpy(ref.net))
     b, p = synth_positions(B, seed=B + ch + 7)
     x = encode_batch(b, p)
-    prev = lib.azg_pv_set_tuning(19, 0)
+    prev = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 0)
     try:
         p32, v32 = m.predict(x)
-        lib.azg_pv_set_tuning(19, cls)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, cls)
         p16, v16 = m.predict(x)
     finally:
-        lib.azg_pv_set_tuning(19, prev)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev)
     r64 = RefModel(blocks, ch, dtype=torch.float64)
     r64.net.load_state_dict({k: (v.double() if v.dtype.is_floating_point else v)
                              for k, v in ref.net.state_dict().items()})
@@ -591,24 +592,24 @@ def test_board16_split_bitwise_equals_one_workgroup(B):
     boards, players = synth_positions(B, seed=100 + B)
     bi8, pl8 = np.asarray(boards, np.int8).reshape(B, 225), np.asarray(players, np.int8)
     x = encode_batch(boards, players)
-    prev = lib.azg_pv_set_tuning(52, 0)
+    prev = lib.azg_pv_set_tuning(TUNE.BOARD16_SPLIT_MAX, 0)
     try:
         p0, v0 = m.predict_boards(bi8, pl8)
         q0, w0 = m.predict(x)
-        lib.azg_pv_set_tuning(52, 85)
+        lib.azg_pv_set_tuning(TUNE.BOARD16_SPLIT_MAX, 85)
         p1, v1 = m.predict_boards(bi8, pl8)
         q1, w1 = m.predict(x)
         assert np.array_equal(p1, p0) and np.array_equal(v1, v0)
         assert np.array_equal(q1, q0) and np.array_equal(w1, w0)
         eng.tower_diag_clear()
         r0 = eng.recoveries
-        lib.azg_pv_set_tuning(14, 0)
+        lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, 0)
         try:
             p2, v2 = m.predict_boards(bi8, pl8)
         finally:
-            lib.azg_pv_set_tuning(14, -1)
+            lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, -1)
         assert np.array_equal(p2, p0) and np.array_equal(v2, v0)
         assert eng.recoveries == r0 + 1 and eng.tower_diag()["timeouts"] > 0
         eng.check_status()
     finally:
-        lib.azg_pv_set_tuning(52, prev)
+        lib.azg_pv_set_tuning(TUNE.BOARD16_SPLIT_MAX, prev)

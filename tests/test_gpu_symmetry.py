@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import has_gpu
+from _native import TUNE
 from oracle.boards import synth_positions
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
@@ -106,13 +107,13 @@ def test_per_board_symmetry_is_bitwise_the_host_transform(blocks, ch, B, seed):
     if (blocks, ch, B) == (1, 64, 5):   # the VALU reference stem (tuning key 9 = 0): the same bits
         import _native
         lib = _native.load_library()
-        prev = lib.azg_pv_set_tuning(9, 0)
+        prev = lib.azg_pv_set_tuning(TUNE.STEM_KERNEL, 0)
         try:
             pv, vv = m.predict_boards(b, p, masked=False, symmetry=syms)
             rv, _ = m.predict_boards(b, p, masked=True, symmetry=syms)
             mv, mvv = m.predict_boards(b, p, masked=False, symmetry="mean8")
         finally:
-            lib.azg_pv_set_tuning(9, prev)
+            lib.azg_pv_set_tuning(TUNE.STEM_KERNEL, prev)
         assert np.array_equal(pv, probs) and np.array_equal(vv, values) and np.array_equal(rv, priors)
         assert np.array_equal(mv, seq_mean8(P)) and np.array_equal(mvv, seq_mean8(V))
 
@@ -196,12 +197,12 @@ def test_recovery_recomputes_with_the_same_symmetries():
     with torch.no_grad():
         m.net.bn.weight.mul_(1e5)
     m.engine.mark_dirty()
-    prev_h3 = lib.azg_pv_set_tuning(19, 0)
+    prev_h3 = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, 0)
     try:
         want_sym = m.predict_boards(b, p, masked=True, symmetry=syms)
         want_mean = m.predict_boards(b, p, masked=True, symmetry="mean8")
         plain = m.predict_boards(b, p, masked=True)
-        lib.azg_pv_set_tuning(19, prev_h3)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev_h3)
         m.engine.tower_diag_clear()
         got_sym = m.predict_boards(b, p, masked=True, symmetry=syms)
         d = m.engine.tower_diag()
@@ -214,7 +215,7 @@ def test_recovery_recomputes_with_the_same_symmetries():
         assert not np.array_equal(got_sym[0], plain[0])
         assert lib.azg_pv_status(m.engine.h) == 0
     finally:
-        lib.azg_pv_set_tuning(19, prev_h3)
+        lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev_h3)
         with torch.no_grad():
             m.net.bn.weight.copy_(gamma)
         m.engine.mark_dirty()

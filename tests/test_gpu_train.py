@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import golden_state, has_gpu, load_golden
+from _native import TUNE
 from oracle.boards import encode_batch, synth_positions, synth_targets
 from oracle.ref_net import RefModel, load_numpy_state, state_to_numpy
 
@@ -338,7 +339,8 @@ def train_state_after(x, pi, z, blocks, ch, steps=2, seed=3):
     return got
 
 
-@pytest.mark.parametrize("key,values", [(23, (1, 0)), (24, (1, 0)), (44, (0, 512, 97)), (48, (1, 0))])
+@pytest.mark.parametrize("key,values", [(TUNE.TRAIN_FUSE_APPLY.value, (1, 0)), (TUNE.TRAIN_FUSE_FINALIZE.value, (1, 0)),
+                                        (TUNE.TRAIN_APPLY_GRID.value, (0, 512, 97)), (TUNE.WGRAD_TILE.value, (1, 0))])
 def test_train_schedule_keys_bitwise(key, values):
     """The train step's product tuning keys change only the schedule: where the forward
     BN applies run (23: folded into the next conv's halo staging, or separate passes),
@@ -367,7 +369,8 @@ def test_train_schedule_keys_bitwise(key, values):
         lib.azg_pv_set_tuning(key, prev)
 
 
-@pytest.mark.parametrize("key,value", [(27, 16), (27, 64), (49, 0), (49, 1)])
+@pytest.mark.parametrize("key,value", [(TUNE.WGRAD_SPLITS.value, 16), (TUNE.WGRAD_SPLITS.value, 64),
+                                       (TUNE.TRAIN_ARITH.value, 0), (TUNE.TRAIN_ARITH.value, 1)])
 @pytest.mark.parametrize("tag,blocks,ch,B", [("6x128", 6, 128, 128), ("3x64", 3, 64, 37)])
 def test_train_sum_order_variants_match_oracle(key, value, tag, blocks, ch, B):
     """The weight-grad split count (key 27) changes an fp32 summation order, and key 49 = 0 / 1
@@ -417,7 +420,7 @@ def test_train_h3_range_overflow_is_redone_in_fp32():
     b, p = synth_positions(32, seed=91)
     x = encode_batch(b, p)
     pi, z = synth_targets(32, seed=92)
-    prev = lib.azg_pv_set_tuning(49, 2)
+    prev = lib.azg_pv_set_tuning(TUNE.TRAIN_ARITH, 2)
     try:
         # 1. the device skip alone (pipelined call: no redo)
         m = _overflow_model()
@@ -434,14 +437,14 @@ def test_train_h3_range_overflow_is_redone_in_fp32():
         got = m.train_batch(x, pi, z)
         assert all(np.isfinite(v) for v in got.values()), got
         assert m.engine.train_recoveries == 1 and m.engine.train_skips() == 2
-        lib.azg_pv_set_tuning(49, 0)
+        lib.azg_pv_set_tuning(TUNE.TRAIN_ARITH, 0)
         r = _overflow_model()
         want = r.train_batch(x, pi, z)
-        lib.azg_pv_set_tuning(49, 2)
+        lib.azg_pv_set_tuning(TUNE.TRAIN_ARITH, 2)
         assert got == want, (got, want)
         assert all(torch.equal(a, c) for a, c in zip(_full_state(m), _full_state(r))), "redo != key-49 = 0 step"
         print(f"overflow step redone in fp32: losses {got}")
         m.engine.clear_status()
         assert lib.azg_pv_status(m.engine.h) == 0 and m.engine.train_skips() == 0
     finally:
-        lib.azg_pv_set_tuning(49, prev)
+        lib.azg_pv_set_tuning(TUNE.TRAIN_ARITH, prev)
