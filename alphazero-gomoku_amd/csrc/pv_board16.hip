@@ -29,6 +29,15 @@
 // conflict-free for every tap shift (a 16-lane bank group reads rows b + {0-3, 12-15} at
 // slot k and b + {4-11} at slot k ^ 1, for any b), the B reads (weight rows, b = 0) and the
 // epilogue's 4-B stores too.
+//
+// A-row offsets: which row a lane reads for (fragment, tap) depends only on its pixel and
+// the tap, so the workgroup builds once a table of q * 128 + 16 (q & 6) -- the byte offset
+// of neighbour row q (the zero row off the board) inside a group image, its slot key folded
+// in -- for pixel 80 mg + 16 f + r16 and tap 0..8, laid out [mg][r16][tap][f] (6 u32 per tap:
+// 8-B aligned wide reads; the 16 lanes of a fragment row 54 words apart, every bank once;
+// the four kb lanes of a pixel read one address).  A step's address is then
+// (entry ^ 16 kb) + the group's base, and (entry ^ 16 kb ^ 64) + base for the lo half: one
+// v_xad_u32 each.
 #include "pv_internal.h"
 
 namespace azg {
@@ -40,7 +49,10 @@ constexpr int kB16Stage = kB16C * 128;                        // one (tap, cg) w
 constexpr int kB16Act = 2 * kB16Stage;                        // LDS: [2] weight stages, then the activations
 constexpr int kB16Prow = kB16Act + kB16Groups * kB16Rows * 128;
 constexpr int kB16Hw = kB16Prow + 240 * 4;                    // the heads' 1x1 weights [3][128] (fused projection)
-constexpr int kB16Lds = kB16Hw + 3 * kB16C * 4;               // 150,976 B: one workgroup per CU
+constexpr int kB16Tab = kB16Hw + 3 * kB16C * 4;               // the A-row offset table (below)
+constexpr int kB16TabLane = 9 * 6 * 4;                        // one (mg, r16) lane class: [tap][5 fragments + 1 pad] u32
+constexpr int kB16Lds = kB16Tab + 3 * 16 * kB16TabLane;       // 161,344 B: one workgroup per CU
+static_assert(kB16Lds <= 160 * 1024, "gfx950: 160 KiB of LDS per workgroup");
 constexpr int kB16Waves = 12;
 constexpr int kB16Threads = 64 * kB16Waves;
 constexpr int kB16SplitThreads = 512;                         // SPLIT: 8 waves (80x16 tiles), one pixel third of a board
@@ -270,7 +282,8 @@ __device__ __forceinline__ void b16_exchange(const Board16Args& a, char* lds, in
 
 extern int g_board_abl;
 // ABL: timing ablations of the study build (key 51): 1 no DMA wait, 2 no barrier, 4 no epilogue
-// (the accumulators kept live), 8 fixed A rows, 64 no residual loads; the product runs ABL 0
+// (the accumulators kept live), 8 fixed A rows (no table reads: the ceiling of the A-row
+// addressing), 64 no residual loads; the product runs ABL 0
 // SPLIT (small batches): three 8-wave workgroups per board, workgroup 3 b + mg computing pixels
 // 80 mg .. 80 mg + 79 of every channel (wave = one 16-channel fragment: 80x16 tiles), the same
 // per-element MFMA chains (bitwise the unsplit tower), conv outputs' boundary rows exchanged
@@ -295,23 +308,23 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
     if (tid < kB16Groups * 32) ((float*)(lds + kB16Act + ((tid >> 5) * kB16Rows + PIX) * 128))[tid & 31] = 0.f;
     if (a.hout)
         for (int i = tid; i < 3 * kB16C; i += NT) ((float*)(lds + kB16Hw))[i] = i < 2 * kB16C ? a.hwp[i] : a.hwv[i - 2 * kB16C];
-
-    // this lane's A rows (pixel 80 mg + 16 f + r16 of fragment f) and the taps on the board
-    int pf[5];
-    unsigned tm[5];
-#pragma unroll
-    for (int f = 0; f < 5; ++f) {
-        const int p = 80 * mg + 16 * f + r16;
+    // the A-row offset table: entry (lane class lc = 16 mg + r16, tap, fragment f)
+    for (int i = tid; i < 3 * 16 * 9 * 5; i += NT) {
+        const int f = i % 5, tap = (i / 5) % 9, lc = i / 45;
+        const int p = 80 * (lc >> 4) + 16 * f + (lc & 15);
         const int py = p / BOARD, px = p - py * BOARD;
-        unsigned t = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int yy = py + k / 3 - 1, xx = px + k % 3 - 1;
-            if (p < PIX && yy >= 0 && yy < BOARD && xx >= 0 && xx < BOARD) t |= 1u << k;
-        }
-        pf[f] = p;
-        tm[f] = t;
+        const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+        const int q = p < PIX && yy >= 0 && yy < BOARD && xx >= 0 && xx < BOARD ? yy * BOARD + xx : PIX;
+        ((unsigned*)(lds + kB16Tab))[(lc * 9 + tap) * 6 + f] = (unsigned)(q * 128 + 16 * (q & 6));
     }
+
+    // this lane's rows of the table (pixel 80 mg + 16 f + r16 of fragment f), its slot bits
+    // for the hi and the lo half
+    const char* tabl = lds + kB16Tab + (16 * mg + r16) * kB16TabLane;
+    const unsigned kx = 16u * (unsigned)kb, kxl = kx ^ 64u;
+    int pf[5];   // (study build, ABL 8: the lane's own rows)
+#pragma unroll
+    for (int f = 0; f < 5; ++f) pf[f] = 80 * mg + 16 * f + r16;
     // B fragments: weight row n = 32 ng + 16 j + r16, slot kb (hi) / kb ^ 4 (lo), keyed by n & 6 = r16 & 6
     const int bh0 = (32 * ng + 16 * nb + r16) * 128 + 16 * (kb ^ (r16 & 6));
     const int bl0 = bh0 ^ 64;
@@ -351,7 +364,7 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
         dma(a.wp[0], 0, 0);
         dma(a.wp[0], 1, 1);
     }
-    __syncthreads();   // poff / zero rows
+    __syncthreads();   // poff / zero rows / the offset table
     for (; board < a.B; board += bstride) {
         float* xb = a.x + (size_t)board * PADPIX * kB16C;
         const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(xb, (short)0, PADPIX * kB16C * 4, 0x00020000);
@@ -401,29 +414,36 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
             const float* wl = a.wp[l];
             const float* wn = l + 1 < nl ? a.wp[l + 1] : a.wp[0];
             const bool more = l + 1 < nl || more_boards;
-            // A rows of (cg, tap) for fragment f: neighbour pixel q (the group's zero row off
-            // the board), rebuilt per tap (45 hoisted row addresses would not fit)
-            auto arow = [&](int cg, int tap, int f) {
-                if constexpr ((ABL & 8) != 0) return kB16Act + (cg * kB16Rows + pf[f]) * 128 + 16 * (kb ^ (pf[f] & 6));
-                asm volatile("" : "+v"(tm[f]), "+v"(pf[f]));
-                const int d = (tap / 3 - 1) * BOARD + (tap % 3 - 1);
-                const int q = ((tm[f] >> tap) & 1) ? pf[f] + d : PIX;
-                return kB16Act + (cg * kB16Rows + q) * 128 + 16 * (kb ^ (q & 6));
+            // A rows of a tap for the five fragments: the table's entries (three 8-B reads),
+            // then per group cg the hi or lo half's address of fragment f
+            unsigned en[6];
+            auto entries = [&](int tap) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const uint2 e2 = *(const uint2*)(tabl + tap * 24 + 8 * k);
+                    en[2 * k] = e2.x, en[2 * k + 1] = e2.y;
+                }
+            };
+            auto arow = [&](int cg, int f, bool lo) {
+                if constexpr ((ABL & 8) != 0)
+                    return (kB16Act + (cg * kB16Rows + pf[f]) * 128 + 16 * (kb ^ (pf[f] & 6))) ^ (lo ? 64 : 0);
+                return (int)((en[f] ^ (lo ? kxl : kx)) + (unsigned)(kB16Act + cg * kB16Rows * 128));
             };
             // step 0's operands; then every wave holds chunk 0's B fragments and stage 0 may
             // be refilled
             f16x8 bh[NJ], bl[NJ], ah[5], al[5];
+            if constexpr (!(ABL & 8)) entries(0);
 #pragma unroll
             for (int f = 0; f < 5; ++f) {
-                const int ao = arow(0, 0, f);
-                al[f] = *(const f16x8*)(lds + (ao ^ 64));
-                ah[f] = *(const f16x8*)(lds + ao);
+                al[f] = *(const f16x8*)(lds + arow(0, f, true));
+                ah[f] = *(const f16x8*)(lds + arow(0, f, false));
             }
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 bh[j] = *(const f16x8*)(lds + bh0 + j * 2048);
                 bl[j] = *(const f16x8*)(lds + bl0 + j * 2048);
             }
+            if constexpr (!(ABL & 8)) entries(1);   // step 1's rows (read during step 0)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __syncthreads();
             // K32 step s = 9 cg + tap computes from registers read during step s - 1: chunk
@@ -439,7 +459,7 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
                     if (tap < 7 || cg + 1 < kB16Groups) dma(wl, s + 2, buf);
                     else if (more) dma(wn, s + 2 - kB16Steps, buf);
                     const bool nx = tap < 8 || cg + 1 < kB16Groups;   // (scalar)
-                    const int ncg = tap < 8 ? cg : cg + 1, ntap = tap < 8 ? tap + 1 : 0;
+                    const int ncg = tap < 8 ? cg : cg + 1;
                     const char* bn = lds + (buf ^ 1) * kB16Stage;
                     // per element the chain lo_a hi_b, hi_a hi_b, hi_a lo_b, product-major over
                     // the 10 tiles (no MFMA waits on the one before)
@@ -449,13 +469,9 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
                         for (int j = 0; j < NJ; ++j)
                             acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[f], bh[j], acc[f][j], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    int ao[5];
                     if (nx) {
 #pragma unroll
-                        for (int f = 0; f < 5; ++f) {
-                            ao[f] = arow(ncg, ntap, f);
-                            al[f] = *(const f16x8*)(lds + (ao[f] ^ 64));
-                        }
+                        for (int f = 0; f < 5; ++f) al[f] = *(const f16x8*)(lds + arow(ncg, f, true));
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -479,6 +495,14 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) bl[j] = *(const f16x8*)(bn + bl0 + j * 2048);
                         __builtin_amdgcn_sched_barrier(0);
+                        // the hi addresses release the entries: step s + 2's are fetched here, ahead
+                        // of the hi reads, so the wait below covers them and no A read waits on one
+                        int ao[5];
+#pragma unroll
+                        for (int f = 0; f < 5; ++f) ao[f] = arow(ncg, f, false);
+                        if constexpr (!(ABL & 8))
+                            if (tap < 7 || cg + 1 < kB16Groups) entries((tap + 2) % 9);
+                        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int f = 0; f < 5; ++f) ah[f] = *(const f16x8*)(lds + ao[f]);
                     }
@@ -486,7 +510,8 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
                     // step s + 1's reads, and every wave's reads of chunk s + 1 are complete (its
                     // stage takes chunk s + 3)
                     // (the barrier waits for this wave's B reads of chunk s + 1, issued before its
-                    // A reads: the 5 activation reads may stay in flight -- no DMA writes there)
+                    // A reads and the table's: the 5 activation reads may stay in flight -- no DMA
+                    // writes there)
                     if constexpr (!(ABL & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(5)" ::: "memory");
                     if constexpr (!(ABL & 2)) __builtin_amdgcn_s_barrier();
                 }
@@ -511,7 +536,8 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
             else if (!SPLIT && a.hout)
                 bad = b16_epilogue<true, false, (ABL >> 6), true, NJ>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
             else bad = b16_epilogue<true, false, (ABL >> 6), false, NJ>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
-            if (bad && a.ring_ovf && a.seq)
+            // (a timing ablation's garbage is not posted: the host-mapped stores would be what it times)
+            if (ABL == 0 && bad && a.ring_ovf && a.seq)
                 __hip_atomic_store(a.ring_ovf + (a.seq & (kTowerRing - 1)), a.seq, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
             // the next conv reads what every wave wrote to LDS.  The block-output stores need
