@@ -597,7 +597,10 @@ int32_t ensure_eval_workspace(azg_pv* h, int images, hipStream_t st)
     free_eval_workspace(h);
     {
         hipError_t e = hipMalloc(&h->tower_sync, tower_sync_bytes(2 * h->NB, cap * PIX));
-        if (e != hipSuccess) return fail("ensure_eval_workspace: hipMalloc(tower sync)", e);
+        // azg_pv_tower_status reads its timeout word before any tower launch has written it
+        // (a handle that has only run per-layer convs or the board tower): 0, not what hipMalloc left
+        if (e == hipSuccess) e = hipMemsetAsync(h->tower_sync, 0, tower_sync_bytes(2 * h->NB, cap * PIX), st);
+        if (e != hipSuccess) return fail("ensure_eval_workspace: tower sync words", e);
         e = hipMalloc(&h->tower_prod, tower_prod_bytes(2 * h->NB, cap * PIX));
         if (e == hipSuccess) e = hipMemsetAsync(h->tower_prod, 0, tower_prod_bytes(2 * h->NB, cap * PIX), st);
         if (e != hipSuccess) return fail("ensure_eval_workspace: tower producer records", e);

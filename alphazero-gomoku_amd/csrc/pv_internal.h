@@ -161,8 +161,6 @@ hipError_t launch_pack_h3(const float* params, const int64_t* offs, int nl, int 
                           const float* scale, int* exps, void* wp16, float* scale16, float* inv, hipStream_t st);
 hipError_t launch_pack_h3_dgrad(const float* params, const int64_t* offs, int nl, int C, const int* exps, void* wd16,
                                 hipStream_t st);
-hipError_t launch_fold_bn(const float* params, const float* stats, const void* desc, int nlayers,
-                          float* scale, float* shift, hipStream_t st);
 
 // What one eval forward reads and writes.  `batch` counts BOARDS, here and in every host
 // function that takes an EvalCall; the kernel launchers' B / M count IMAGES (images():

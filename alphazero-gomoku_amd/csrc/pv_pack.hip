@@ -55,16 +55,85 @@ __global__ void transpose_kernel(const float* __restrict__ src, float* __restric
     }
 }
 
-__global__ void fold_bn_kernel(const float* __restrict__ params, const float* __restrict__ stats,
-                               const BnDesc* __restrict__ desc, float* __restrict__ scale,
-                               float* __restrict__ shift)
+// ---- activation exponents of the eval fold ----
+// The split-fp16 eval convs (pv_halo.h VAR bit 64, pv_h3.h, pv_board*.hip) stage every
+// activation x as hi = fp16(x), lo = fp16(x - hi): lo is a normal fp16 only while
+// |x| >= ~2^-3 and carries a fixed 2^-25 absolute error below, which the next BN's
+// gamma / sqrt(var + eps) (up to 316) scales back up.  A net whose BN gammas have shrunk
+// has such activations, so the fold carries the trunk activation as 2^T x and block b's
+// mid activation as 2^m_b x:
+//   stem  scale, shift * 2^T          bn1_b  scale * 2^(m_b - T), shift * 2^m_b
+//   heads scale * 2^-T                bn2_b  scale * 2^(T - m_b), shift * 2^T
+// Powers of two commute with the ReLUs and the residual add, and every factor is exact:
+// outputs change only through which bits hi / lo capture.  The exponents come from the
+// parameters alone.  A(bn) = max_c(|beta_c| + 4 |gamma_c|) bounds the BN's output at 4
+// sigma; an exponent lifts a bound below kActBand into [4, 8):
+//   m_b = lift(A(bn1_b));  T = min(lift(A(stem)), kActTrunkCap - ilogb(A(stem) + sum_b A(bn2_b)))
+// The cap keeps the trunk sum's bound below 2^13 (fp16 overflows at 2^16; the overflow
+// guard stays the backstop).  Every bound of at least kActBand (gamma >= 1/16: seeded,
+// calibrated and trained nets) gives exponent 0 and the fold is bit for bit the plain one.
+// oracle/value_range.py act_exponents restates the rule.
+constexpr float kActBand = 0.25f;
+constexpr int kActTrunkCap = 12;
+constexpr int kActMaxExp = 40;
+constexpr int kActMaxBn = 256;   // BN layers a fold workgroup can bound (launch_repack_all checks)
+
+__device__ __forceinline__ int act_lift(float bound)
 {
-    const BnDesc d = desc[blockIdx.x];
+    if (!(bound > 0.f && bound < kActBand)) return 0;
+    const int e = 2 - ilogbf(bound);
+    return e < kActMaxExp ? e : kActMaxExp;
+}
+
+// The fold of BN layer j (desc order: stem, (bn1, bn2) per block, policy, value; nl = 2 x
+// blocks) by one workgroup of 256: eval-mode BN as ATen's CPU inference path (file header)
+// times the activation exponents above.
+__device__ __forceinline__ void fold_bn_layer(const float* __restrict__ params, const float* __restrict__ stats,
+                                              const BnDesc* __restrict__ desc, int nbn, int nl, int j,
+                                              float* __restrict__ scale, float* __restrict__ shift)
+{
+    __shared__ unsigned bound[kActMaxBn];   // bits of a non-negative float: their order is the floats' order
+    __shared__ int ex[2];                   // the exponents of this layer's scale and shift
+    for (int i = threadIdx.x; i < nbn; i += blockDim.x) bound[i] = 0u;
+    __syncthreads();
+    // the bounds this layer's exponents need: the stem's and every bn2's (T), its block's bn1 (m_b)
+    const int own1 = j >= 1 && j <= nl ? ((j - 1) | 1) : -1;   // bn1 of j's block (bn1_b: 1 + 2b, bn2_b: 2 + 2b)
+    for (int i = 0; i <= nl && i < nbn; ++i) {
+        if (i != 0 && (i & 1) && i != own1) continue;
+        const BnDesc d = desc[i];
+        float m = 0.f;
+        for (int c = threadIdx.x; c < d.c; c += blockDim.x)
+            m = fmaxf(m, fabsf(params[d.beta_off + c]) + 4.f * fabsf(params[d.gamma_off + c]));
+        if (m > 0.f) atomicMax(&bound[i], __float_as_uint(m));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float a_stem = __uint_as_float(bound[0]);
+        float u = a_stem;
+        for (int i = 2; i <= nl; i += 2) u += __uint_as_float(bound[i]);
+        int T = act_lift(a_stem);
+        if (T) {
+            const int cap = kActTrunkCap - ilogbf(u);
+            T = T < cap ? T : cap;
+            T = T > 0 ? T : 0;
+        }
+        const int m = own1 > 0 ? act_lift(__uint_as_float(bound[own1])) : 0;
+        int es, eh;
+        if (j == 0) { es = T; eh = T; }
+        else if (j > nl) { es = -T; eh = 0; }
+        else if (j == own1) { es = m - T; eh = m; }
+        else { es = T - m; eh = T; }
+        ex[0] = es;
+        ex[1] = eh;
+    }
+    __syncthreads();
+    const int es = ex[0], eh = ex[1];
+    const BnDesc d = desc[j];
     for (int c = threadIdx.x; c < d.c; c += blockDim.x) {
         const float invstd = 1.0f / sqrtf(stats[d.stat_off + d.c + c] + BN_EPS);
         const float alpha = invstd * params[d.gamma_off + c];
-        scale[d.out_off + c] = alpha;
-        shift[d.out_off + c] = params[d.beta_off + c] - stats[d.stat_off + c] * alpha;
+        scale[d.out_off + c] = ldexpf(alpha, es);
+        shift[d.out_off + c] = ldexpf(params[d.beta_off + c] - stats[d.stat_off + c] * alpha, eh);
     }
 }
 
@@ -124,13 +193,7 @@ __global__ __launch_bounds__(256) void repack_all_kernel(const RepackArgs a)
             a.wfc[idx] = v;
         }
     } else if (blockIdx.x < (unsigned)a.nbn) {
-        const BnDesc d = a.desc[blockIdx.x];
-        for (int c = threadIdx.x; c < d.c; c += blockDim.x) {
-            const float invstd = 1.0f / sqrtf(a.stats[d.stat_off + d.c + c] + BN_EPS);
-            const float alpha = invstd * a.params[d.gamma_off + c];
-            a.scale[d.out_off + c] = alpha;
-            a.shift[d.out_off + c] = a.params[d.beta_off + c] - a.stats[d.stat_off + c] * alpha;
-        }
+        fold_bn_layer(a.params, a.stats, a.desc, a.nbn, a.nl, (int)blockIdx.x, a.scale, a.shift);
     }
 }
 
@@ -144,6 +207,7 @@ hipError_t launch_repack_all(const float* params, const int64_t* conv_offs, int 
 {
     RepackArgs a{params, conv_offs, wp, wd, C, nl, stem_w, ws, wpf, wv1, wfc, stats, (const BnDesc*)desc, nbn,
                  scale, shift, part == 1 ? nl : 0, part == 2 ? nl : -1};
+    if (nbn > kActMaxBn) return hipErrorInvalidValue;
     int nb = (9 * C * C + 255) / 256;
     nb = nb > 256 ? 256 : nb;
     nb = nb < nbn ? nbn : nb;
@@ -320,14 +384,6 @@ hipError_t launch_pack_fc(const float* wpf, const float* wv1, float* wfc, hipStr
 hipError_t launch_transpose(const float* src, float* dst, int R, int Cc, hipStream_t st)
 {
     hipLaunchKernelGGL(transpose_kernel, dim3(nblk(R * Cc)), dim3(256), 0, st, src, dst, R, Cc);
-    return hipGetLastError();
-}
-
-hipError_t launch_fold_bn(const float* params, const float* stats, const void* desc, int nlayers,
-                          float* scale, float* shift, hipStream_t st)
-{
-    hipLaunchKernelGGL(fold_bn_kernel, dim3(nlayers), dim3(256), 0, st, params, stats,
-                       (const BnDesc*)desc, scale, shift);
     return hipGetLastError();
 }
 

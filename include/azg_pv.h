@@ -358,7 +358,7 @@ int32_t azg_pv_set_tuning(int32_t key, int32_t value);
  * forward (predict, predict_boards, BoardEvaluator.wait), so a timeout costs one
  * per-layer forward instead of an error. */
 /* Error word of the last tower launch on this handle: 1 if one of its waits timed
- * out (synchronises `stream`). */
+ * out, 0 otherwise and before the handle has launched a tower (synchronises `stream`). */
 int32_t azg_pv_tower_status(azg_pv* h, void* stream);
 uint32_t azg_pv_last_seq(const azg_pv* h);
 int32_t azg_pv_recover(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream);

@@ -10,6 +10,7 @@ from conftest import golden_state, has_gpu, load_golden
 from _native import TUNE
 from oracle.boards import encode_batch, synth_positions, valid_mask
 from oracle.ref_net import RefModel, load_numpy_state, state_to_numpy
+from oracle.value_range import calib_bn  # noqa: F401  (moved to the oracle; importable from here as before)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
 
@@ -137,24 +138,6 @@ def test_split_forward_on_trained_weights_matches_oracle32(blocks, ch, seed, B, 
               f"|gpu-fp64|={np.abs(got[:n64] - r_64).max():.2e} |cpu32-fp64|={np.abs(r32[:n64] - r_64).max():.2e}")
         assert d32 <= TOL, (name, d32)
     argmax_check(probs, rp, b)
-
-
-def calib_bn(ref, seed):
-    """Give BN running stats the statistics of real activations (train-mode passes
-    without optimizer steps), as a trained net has."""
-    b, p = synth_positions(64, seed=seed)
-    x = torch.from_numpy(encode_batch(b, p))
-    ref.net.train()
-    for mod in ref.net.modules():
-        if isinstance(mod, torch.nn.BatchNorm2d):
-            mod.momentum = None   # cumulative average
-    with torch.no_grad():
-        for _ in range(3):
-            ref.net(x)
-    for mod in ref.net.modules():
-        if isinstance(mod, torch.nn.BatchNorm2d):
-            mod.momentum = 0.1
-    ref.net.eval()
 
 
 @pytest.mark.parametrize("blocks,ch,cls,n", [(3, 64, 2, 130), (6, 128, 2, 600), (6, 128, 1, 600)])
