@@ -58,6 +58,8 @@ _SIGS = {
     "azg_pv_forward": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P]),
     "azg_pv_forward_boards": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, _P, _P, _P, _P]),
     "azg_pv_forward_boards_sym": (ctypes.c_int32, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),
+    "azg_pv_set_eval_precision": (ctypes.c_int32, [_P, ctypes.c_int32]),
+    "azg_pv_get_eval_precision": (ctypes.c_int32, [_P]),
     "azg_pv_train_backward": (ctypes.c_int32, [_P, _P, _P, _P, ctypes.c_int32, _P, _P]),
     "azg_pv_train_apply": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,

@@ -83,6 +83,20 @@ int main()
             CHECK(azg_pv_forward_boards_sym(h, &i8, &i8, &i8, 1, 2048, &dummy, &dummy, &dummy, nullptr) != 0);
             CHECK(std::strstr(azg_pv_last_error(), "not bound") != nullptr);
         }
+        {   // azg_pv_set_eval_precision / azg_pv_get_eval_precision: checked before any device call
+            const bool ok16 = shapes[s][1] == 128 && shapes[s][0] >= 1;   // fp16: C = 128, 1..32 blocks
+            CHECK(azg_pv_get_eval_precision(h) == AZG_PV_EVAL_EXACT);
+            CHECK(azg_pv_set_eval_precision(h, 2) != 0 && azg_pv_set_eval_precision(h, -1) != 0);
+            CHECK(std::strstr(azg_pv_last_error(), "azg_pv_set_eval_precision") != nullptr);
+            CHECK(azg_pv_get_eval_precision(h) == AZG_PV_EVAL_EXACT);
+            CHECK((azg_pv_set_eval_precision(h, AZG_PV_EVAL_FP16) == 0) == ok16);
+            if (!ok16) CHECK(std::strstr(azg_pv_last_error(), "128") != nullptr);
+            CHECK(azg_pv_get_eval_precision(h) == (ok16 ? AZG_PV_EVAL_FP16 : AZG_PV_EVAL_EXACT));
+            // the forwards' argument checks do not depend on the precision (the handle is unbound)
+            CHECK(azg_pv_forward(h, &dummy, 1, &dummy, &dummy, nullptr, nullptr) != 0);
+            CHECK(azg_pv_set_eval_precision(h, AZG_PV_EVAL_EXACT) == 0);
+            CHECK(azg_pv_get_eval_precision(h) == AZG_PV_EVAL_EXACT);
+        }
         CHECK(azg_pv_train_backward(h, &dummy, &dummy, &dummy, 4, &dummy, nullptr) != 0);
         CHECK(azg_pv_train_apply(h, &dummy, &dummy, 1, 1e-3f, 0.9f, 0.999f, 1e-8f, 1e-4f, 3.f, nullptr, nullptr) != 0);
         CHECK(azg_pv_destroy(h) == 0);
@@ -103,6 +117,8 @@ int main()
     CHECK(azg_pv_grad_count(nullptr) == -1);
     CHECK(azg_pv_train_fp32_once(nullptr) != 0);
     CHECK(azg_pv_last_seq(nullptr) == 0);
+    CHECK(azg_pv_set_eval_precision(nullptr, AZG_PV_EVAL_EXACT) != 0);
+    CHECK(azg_pv_get_eval_precision(nullptr) == -1);
     CHECK(azg_pv_tower_diag_clear(nullptr, nullptr) != 0);
     CHECK(azg_pv_bind(nullptr, nullptr, nullptr, nullptr) != 0);
     // replay gather: every argument is checked before any device call

@@ -46,7 +46,8 @@ constexpr int kB16C = 128;
 constexpr int kB16Groups = kB16C / 32;
 constexpr int kB16Rows = PIX + 1;                             // 225 pixels + the zero row
 constexpr int kB16Stage = kB16C * 128;                        // one (tap, cg) weight chunk: 128 rows x [hi 32 | lo 32]
-constexpr int kB16Act = 2 * kB16Stage;                        // LDS: [2] weight stages, then the activations
+constexpr int kB16Stage1 = kB16Stage / 2;                     // the one-product tower's chunk: 128 rows x [hi 32]
+constexpr int kB16Act = 2 * kB16Stage;                        // LDS: [2] weight stages (NP = 1: [4] of 8 KB), then the activations
 constexpr int kB16Prow = kB16Act + kB16Groups * kB16Rows * 128;
 constexpr int kB16Hw = kB16Prow + 240 * 4;                    // the heads' 1x1 weights [3][128] (fused projection)
 constexpr int kB16Tab = kB16Hw + 3 * kB16C * 4;               // the A-row offset table (below)
@@ -61,10 +62,10 @@ static_assert(kB16Img == (int)kB16ImgBytes, "pv_internal.h kB16ImgBytes");
 constexpr int kB16MaxLayers = 2 * kTowerMaxBlocks;
 constexpr int kB16Steps = 9 * kB16Groups;                     // K32 steps (weight chunks) per conv
 static_assert((kB16Groups * kB16Rows * 128) % 256 == 0, "a group's image keeps the 256-B bank phase");
-static_assert(kB16Steps % 2 == 0, "step s of every conv uses stage s & 1");
+static_assert(kB16Steps % 4 == 0, "step s of every conv uses stage s & 1 (one product: s & 3)");
 
 struct Board16Args {
-    const float* wp[kB16MaxLayers];     // split-fp16 packs (pack_h3: [tap*CG + cg][cout][hi 32 | lo 32])
+    const float* wp[kB16MaxLayers];     // split-fp16 packs (pack_h3: [tap*CG + cg][cout][hi 32 | lo 32]; NP = 1: [hi 32])
     const float* scale[kB16MaxLayers];  // H3 BN scale (carries the pack's 2^-e) and shift
     const float* shift[kB16MaxLayers];
     float* x;                           // padded NHWC [B][17][17][128]: stem output in, tower output out
@@ -88,6 +89,7 @@ struct Board16Args {
 
 typedef float b16_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned b16_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned b16_u32x2 __attribute__((ext_vector_type(2)));
 
 // byte offset of (pixel m, channel c) in the fp32 rows of the fused heads projection: 16-B
 // slots keyed by m & 15, so the epilogue's stores and the projection's float4 reads spread
@@ -109,7 +111,11 @@ typedef _Float16 b16_f16x2 __attribute__((ext_vector_type(2)));
 // was non-finite (their sum is: padding accumulators are exactly 0).  F32L (the last conv when
 // the heads are fused): the block output goes to LDS as fp32 rows [pixel][128] instead of HBM.
 // NJ (SPLIT: 1): the wave's 16-channel fragments, from fragment nb of its group.
-template <bool RES, bool TO_LDS, int EABL = 0, bool F32L = false, int NJ = 2>
+// NP = 1 (the one-product fp16 tower): TO_LDS writes the hi halves only, y rounded once to
+// fp16 (one v_cvt_pk per element pair); the even lane of a pair forms the words of pixels i = 0,
+// 1 and the odd lane those of pixels 2, 3 (the partner's H of that pixel pair by one DPP): rows
+// i and i + 2 differ in their key's bit 1, so a store's 32 lanes of a half-wave cover 32 banks.
+template <bool RES, bool TO_LDS, int EABL = 0, bool F32L = false, int NJ = 2, int NP = 3>
 __device__ __forceinline__ bool b16_epilogue(const f32x4 (&acc)[5][NJ], const float* __restrict__ scale,
                                              const float* __restrict__ shift, __amdgpu_buffer_rsrc_t xr, char* lds,
                                              const int* poff, int mg, int cg, int lane, int nb = 0)
@@ -119,7 +125,7 @@ __device__ __forceinline__ bool b16_epilogue(const f32x4 (&acc)[5][NJ], const fl
     // the lane's part of a store offset in a keyed row: slot (ce >> 3) ^ 4 (kb & 1), channel
     // ce & 7, lo half for the odd lane; the tile's 32 (n ^ (i >> 1)) and the row i * 128 are
     // immediates (row m = m0 + i has key 4 (kb & 1) | (i & 2))
-    const int lpart = (16 * ((ce >> 3) ^ (4 * (kb & 1))) + 2 * (ce & 7)) ^ (odd ? 64 : 0);
+    const int lpart = (16 * ((ce >> 3) ^ (4 * (kb & 1))) + 2 * (ce & 7)) ^ (odd && NP != 1 ? 64 : 0);
     // the word of element i (e = 0) / i + 1 (e = 1) from X (own H or L) and Zp (the partner's):
     // even lane (own hi, partner hi), odd lane (partner lo, own lo)
     const unsigned sel0 = odd ? 0x01000504u : 0x05040100u, sel1 = odd ? 0x03020706u : 0x07060302u;
@@ -156,7 +162,8 @@ __device__ __forceinline__ bool b16_epilogue(const f32x4 (&acc)[5][NJ], const fl
         const float (&rv)[NJ][4] = rvf[f];
         char* wrow = lds + kB16Act + (cg * kB16Rows + m0) * 128 + lpart;
 #pragma unroll
-        for (int nn = 0; nn < NJ; ++nn)
+        for (int nn = 0; nn < NJ; ++nn) {
+            unsigned H1[2];   // NP = 1: the fp16 pairs of the lane's pixel pairs
 #pragma unroll
             for (int ip = 0; ip < 2; ++ip) {
                 const int n = nb + nn;
@@ -176,7 +183,10 @@ __device__ __forceinline__ bool b16_epilogue(const f32x4 (&acc)[5][NJ], const fl
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ye[e]), xr,
                                                               vo[2 * ip + e] + 64 * n, 0, 0);
                 }
-                if constexpr (TO_LDS) {
+                if constexpr (TO_LDS && NP == 1) {
+                    const b16_f32x2 yy = {ye[0], ye[1]};
+                    H1[ip] = __builtin_bit_cast(unsigned, __builtin_convertvector(yy, b16_f16x2));
+                } else if constexpr (TO_LDS) {
                     // the lane's two elements split together: H = (hi_i, hi_i+1), L = (lo_i, lo_i+1);
                     // the partner lane's H (to an even lane) or L (to an odd lane) by one DPP
                     // (lo = fp16(y - hi) by v_fma_mix{lo,hi}_f16: the exact fp32 difference rounded
@@ -199,6 +209,19 @@ __device__ __forceinline__ bool b16_epilogue(const f32x4 (&acc)[5][NJ], const fl
                     }
                 }
             }
+            if constexpr (TO_LDS && NP == 1) {
+                const int n = nb + nn;
+                const unsigned X = odd ? H1[1] : H1[0], Z = odd ? H1[0] : H1[1];
+                const unsigned Zp = (unsigned)__builtin_amdgcn_mov_dpp((int)Z, 0xB1, 0xF, 0xF, false);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int i = 2 * odd + e;
+                    const unsigned word = __builtin_amdgcn_perm(Zp, X, e ? sel1 : sel0);
+                    if (f < 4 || m0 + i < PIX)
+                        *(unsigned*)(wrow + i * 128 + 32 * (n ^ odd)) = word;
+                }
+            }
+        }
     }
     return !__builtin_isfinite(chk.x + chk.y);
 }
@@ -288,9 +311,24 @@ extern int g_board_abl;
 // 80 mg .. 80 mg + 79 of every channel (wave = one 16-channel fragment: 80x16 tiles), the same
 // per-element MFMA chains (bitwise the unsplit tower), conv outputs' boundary rows exchanged
 // through L2 (b16_exchange); the tower output goes to x (the heads run unfused).
-template <int ABL, bool SPLIT = false>
+//
+// NP = 1, the one-product fp16 tower (an opt-in eval precision, azg_pv_set_eval_precision): the
+// same loop with one MFMA per product, ah[f] bh[j] -- operands rounded once to fp16, the trunk
+// still carried in fp32.  The activation image keeps its geometry (the lo slots are never
+// written or read: slot key, offset table, zero rows and the heads' fp32 rows carry over).  A
+// weight chunk is the pack's hi halves only, 128 rows x 64 B (the two stages' 32 KB hold four): row
+// n's four 16-B slots at slot ^ b16_wkey(n), which keeps the B fragments' ds_read_b128 lane
+// groups (rows {0-3, 12-15} at slot k with rows {4-11} at slot k ^ 1) on 16 distinct slots of
+// the 256-B bank window (scripts/lab/slot_key_search.py --weights).  With 10 MFMAs per step a
+// wave cannot hide a fragment read behind the product group before it, so step s + 1's
+// fragments are read into a second register set ahead of step s's MFMAs, and chunk s + 3 is
+// issued in step s.
+__device__ __forceinline__ int b16_wkey(int n) { return ((n >> 2) & 3) ^ ((n >> 1) & 2); }
+
+template <int ABL, bool SPLIT = false, int NP = 3>
 __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void board16_tower(const Board16Args a)
 {
+    static_assert(NP == 3 || (NP == 1 && ABL == 0), "one or three products; the timing ablations are the exact form's");
     constexpr int NT = SPLIT ? kB16SplitThreads : kB16Threads;
     constexpr int NJ = SPLIT ? 1 : 2;   // 16-channel fragments per wave
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -326,8 +364,11 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
 #pragma unroll
     for (int f = 0; f < 5; ++f) pf[f] = 80 * mg + 16 * f + r16;
     // B fragments: weight row n = 32 ng + 16 j + r16, slot kb (hi) / kb ^ 4 (lo), keyed by n & 6 = r16 & 6
-    const int bh0 = (32 * ng + 16 * nb + r16) * 128 + 16 * (kb ^ (r16 & 6));
+    // (NP = 1: 64-B rows, slot kb keyed by b16_wkey)
+    const int bh0 = NP == 1 ? (32 * ng + 16 * nb + r16) * 64 + 16 * (kb ^ b16_wkey(r16))
+                            : (32 * ng + 16 * nb + r16) * 128 + 16 * (kb ^ (r16 & 6));
     const int bl0 = bh0 ^ 64;
+    constexpr int kBj = NP == 1 ? 1024 : 2048;   // 16 weight rows on
 
     // weight DMA of one chunk (16 KB, 128 rows x 128 B): wave w moves rows 8 w .. 8 w + 7,
     // waves 0..3 also rows 96 + 8 w ..; lane -> row + lane / 8, LDS slot lane % 8 holding
@@ -336,8 +377,20 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
     const int ws0 = wr0 * 32 + (((lane & 7) ^ (wr0 & 6)) * 4);
     const int wr1 = 96 + 8 * (wid & 3) + (lane >> 3);
     const int ws1 = wr1 * 32 + (((lane & 7) ^ (wr1 & 6)) * 4);
-    auto dma = [&](const float* wl, int s, int buf) {   // chunk s = cg * 9 + tap -> stage buf
+    // NP = 1 (8 KB, 128 rows x 64 B): waves 0..7 move rows 16 w .. 16 w + 15; lane -> row +
+    // lane / 4, LDS slot lane % 4 holding source slot (lane % 4) ^ b16_wkey(row)
+    const int wr2 = 16 * wid + (lane >> 2);
+    const int ws2 = wr2 * 16 + (((lane & 3) ^ b16_wkey(wr2)) * 4);
+    auto dma = [&](const float* wl, int s, int buf) {   // chunk s = cg * 9 + tap -> stage buf (NP = 1: of four)
         const int cg = s / 9, tap = s - cg * 9;
+        if constexpr (NP == 1) {
+            const float* src = wl + (size_t)(tap * kB16Groups + cg) * kB16C * 16;
+            if (SPLIT || wid < 8)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + ws2),
+                                                 (__attribute__((address_space(3))) void*)(lds + buf * kB16Stage1 + wid * 1024),
+                                                 16, 0, 0);
+            return;
+        }
         const float* src = wl + (size_t)(tap * kB16Groups + cg) * kB16C * 32;
         if constexpr (SPLIT) {   // 8 waves: rows 8 (w + 8 k) .. + 7 (row & 6 as for k = 0)
 #pragma unroll
@@ -360,9 +413,10 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
     const int nl = a.nlayers;
     int board = SPLIT ? (int)blockIdx.x / 3 : (int)blockIdx.x;
     const int bstride = SPLIT ? a.B : (int)gridDim.x;
-    if (board < a.B) {   // the first conv's chunks 0 and 1
+    if (board < a.B) {   // the first conv's chunks 0 and 1 (NP = 1: and 2)
         dma(a.wp[0], 0, 0);
         dma(a.wp[0], 1, 1);
+        if constexpr (NP == 1) dma(a.wp[0], 2, 2);
     }
     __syncthreads();   // poff / zero rows / the offset table
     for (; board < a.B; board += bstride) {
@@ -395,7 +449,7 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
                     char* row = lds + kB16Act + (g * kB16Rows + m) * 128;
                     const int o = 16 * ((q4 >> 1) ^ (m & 6)) + (q4 & 1) * 8;
                     *(f16x4*)(row + o) = hi;
-                    *(f16x4*)(row + (o ^ 64)) = lo;
+                    if constexpr (NP != 1) *(f16x4*)(row + (o ^ 64)) = lo;
                 }
             }
         }
@@ -429,91 +483,172 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
                     return (kB16Act + (cg * kB16Rows + pf[f]) * 128 + 16 * (kb ^ (pf[f] & 6))) ^ (lo ? 64 : 0);
                 return (int)((en[f] ^ (lo ? kxl : kx)) + (unsigned)(kB16Act + cg * kB16Rows * 128));
             };
-            // step 0's operands; then every wave holds chunk 0's B fragments and stage 0 may
-            // be refilled
-            f16x8 bh[NJ], bl[NJ], ah[5], al[5];
-            if constexpr (!(ABL & 8)) entries(0);
+            if constexpr (NP == 1) {
+                // one product: 10 MFMAs per step cannot hide a fragment read or a weight chunk's L2
+                // latency behind them, so step s + 1's fragments are read into (bq, aq) ahead of
+                // step s's MFMAs, and the 8-KB chunks go through FOUR stages (the two 16-KB stages'
+                // bytes), chunk s + 3 issued in step s: a chunk has two steps to land (the wait
+                // ending step s leaves the newest DMA in flight).  The table's entries are read by
+                // asm: before a plain LDS read the compiler drains vmcnt (it cannot tell the read
+                // from a DMA's destination), which would end every prefetch at once; the step's
+                // closing wait returns them (in / out operands of the wait: no use moves above it)
+                f16x8 bh[NJ], ah[5], bq[NJ], aq[5];
 #pragma unroll
-            for (int f = 0; f < 5; ++f) {
-                al[f] = *(const f16x8*)(lds + arow(0, f, true));
-                ah[f] = *(const f16x8*)(lds + arow(0, f, false));
-            }
+                for (int f = 0; f < 5; ++f) aq[f] = f16x8{};
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                bh[j] = *(const f16x8*)(lds + bh0 + j * 2048);
-                bl[j] = *(const f16x8*)(lds + bl0 + j * 2048);
-            }
-            if constexpr (!(ABL & 8)) entries(1);   // step 1's rows (read during step 0)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __syncthreads();
-            // K32 step s = 9 cg + tap computes from registers read during step s - 1: chunk
-            // s + 1 was published by the barrier ending step s - 1 and the conv's input is
-            // static, so step s + 1's fragments are read between this step's product groups
-            // (each into the registers its group just released); chunk s + 2 is issued into
-            // the stage chunk s used (read during step s - 1: every wave is past it)
-            for (int cg = 0; cg < kB16Groups; ++cg) {
+                for (int j = 0; j < NJ; ++j) bq[j] = f16x8{};
+                const unsigned taddr = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)tabl;
+                b16_u32x2 e0, e1, e2;
+                auto entries1 = [&](int tap) {
+                    asm volatile("ds_read_b64 %0, %3\n\tds_read_b64 %1, %3 offset:8\n\tds_read_b64 %2, %3 offset:16"
+                                 : "=&v"(e0), "=&v"(e1), "=&v"(e2) : "v"(taddr + 24u * (unsigned)tap) : "memory");
+                };
+                // (aq / bq are operands too: returned by this wait, so no compiler wait precedes the MFMAs)
+#define B16_SETTLED "+v"(e0), "+v"(e1), "+v"(e2), "+v"(aq[0]), "+v"(aq[1]), "+v"(aq[2]), "+v"(aq[3]), "+v"(aq[4])
+                auto settle = [&](bool newest_in_flight) {   // the LDS reads (the asm's too); DMAs but the newest
+                    if (newest_in_flight) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" : B16_SETTLED : : "memory");
+                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : B16_SETTLED : : "memory");
 #pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const int s = cg * 9 + tap;
-                    const int buf = (cg + tap) & 1;   // = s & 1
-                    if (tap < 7 || cg + 1 < kB16Groups) dma(wl, s + 2, buf);
-                    else if (more) dma(wn, s + 2 - kB16Steps, buf);
-                    const bool nx = tap < 8 || cg + 1 < kB16Groups;   // (scalar)
-                    const int ncg = tap < 8 ? cg : cg + 1;
-                    const char* bn = lds + (buf ^ 1) * kB16Stage;
-                    // per element the chain lo_a hi_b, hi_a hi_b, hi_a lo_b, product-major over
-                    // the 10 tiles (no MFMA waits on the one before)
+                    for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(bq[j]));
+                    en[0] = e0.x, en[1] = e0.y, en[2] = e1.x, en[3] = e1.y, en[4] = e2.x, en[5] = e2.y;
+                };
+#undef B16_SETTLED
+                entries1(0);
+                settle(true);
 #pragma unroll
-                    for (int f = 0; f < 5; ++f)
+                for (int f = 0; f < 5; ++f) ah[f] = *(const f16x8*)(lds + arow(0, f, false));
 #pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-                            acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[f], bh[j], acc[f][j], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (nx) {
+                for (int j = 0; j < NJ; ++j) bh[j] = *(const f16x8*)(lds + bh0 + j * kBj);
+                entries1(1);
+                settle(true);
+                __syncthreads();
+                for (int cg = 0; cg < kB16Groups; ++cg) {
 #pragma unroll
-                        for (int f = 0; f < 5; ++f) al[f] = *(const f16x8*)(lds + arow(ncg, f, true));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int f = 0; f < 5; ++f)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-                            acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f], bh[j], acc[f][j], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (nx) {
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) bh[j] = *(const f16x8*)(bn + bh0 + j * 2048);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int f = 0; f < 5; ++f)
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j)
-                            acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f], bl[j], acc[f][j], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (nx) {   // the B reads first: the barrier need only wait for them
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) bl[j] = *(const f16x8*)(bn + bl0 + j * 2048);
-                        __builtin_amdgcn_sched_barrier(0);
-                        // the hi addresses release the entries: step s + 2's are fetched here, ahead
-                        // of the hi reads, so the wait below covers them and no A read waits on one
+                    for (int tap = 0; tap < 9; ++tap) {
+                        const int s = cg * 9 + tap;
+                        const bool nx = tap < 8 || cg + 1 < kB16Groups;   // (scalar)
+                        const int ncg = tap < 8 ? cg : cg + 1;
+                        const char* bn = lds + ((s + 1) & 3) * kB16Stage1;
                         int ao[5];
 #pragma unroll
                         for (int f = 0; f < 5; ++f) ao[f] = arow(ncg, f, false);
-                        if constexpr (!(ABL & 8))
-                            if (tap < 7 || cg + 1 < kB16Groups) entries((tap + 2) % 9);
+                        // chunk s + 3 into the stage chunk s - 1 left (read during step s - 2)
+                        const bool here = tap < 6 || cg + 1 < kB16Groups, issue = here || more;
+                        if (here) dma(wl, s + 3, (s + 3) & 3);
+                        else if (more) dma(wn, s + 3 - kB16Steps, (s + 3) & 3);
+                        if (nx) {
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j) bq[j] = *(const f16x8*)(bn + bh0 + j * kBj);
+#pragma unroll
+                            for (int f = 0; f < 5; ++f) aq[f] = *(const f16x8*)(lds + ao[f]);
+                        }
+                        if (tap < 7 || cg + 1 < kB16Groups) entries1((tap + 2) % 9);
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int f = 0; f < 5; ++f) ah[f] = *(const f16x8*)(lds + ao[f]);
+                        for (int f = 0; f < 5; ++f)
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j)
+                                acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f], bh[j], acc[f][j], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        // chunk s + 2 has landed (this wave's piece; chunk s + 3 may stay in flight)
+                        // and this wave's reads of chunk s + 1 are complete: the barrier publishes
+                        // the one and frees the other's stage
+                        settle(issue);
+                        __builtin_amdgcn_s_barrier();
+                        // (after the conv's last step the copies are dead)
+#pragma unroll
+                        for (int f = 0; f < 5; ++f) ah[f] = aq[f];
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) bh[j] = bq[j];
                     }
-                    // chunk s + 2 has landed (this wave's pieces); the barrier publishes it for
-                    // step s + 1's reads, and every wave's reads of chunk s + 1 are complete (its
-                    // stage takes chunk s + 3)
-                    // (the barrier waits for this wave's B reads of chunk s + 1, issued before its
-                    // A reads and the table's: the 5 activation reads may stay in flight -- no DMA
-                    // writes there)
-                    if constexpr (!(ABL & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(5)" ::: "memory");
-                    if constexpr (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+                }
+            } else {
+                // step 0's operands; then every wave holds chunk 0's B fragments and stage 0 may
+                // be refilled
+                f16x8 bh[NJ], bl[NJ], ah[5], al[5];
+                if constexpr (!(ABL & 8)) entries(0);
+#pragma unroll
+                for (int f = 0; f < 5; ++f) {
+                    al[f] = *(const f16x8*)(lds + arow(0, f, true));
+                    ah[f] = *(const f16x8*)(lds + arow(0, f, false));
+                }
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    bh[j] = *(const f16x8*)(lds + bh0 + j * 2048);
+                    bl[j] = *(const f16x8*)(lds + bl0 + j * 2048);
+                }
+                if constexpr (!(ABL & 8)) entries(1);   // step 1's rows (read during step 0)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __syncthreads();
+                // K32 step s = 9 cg + tap computes from registers read during step s - 1: chunk
+                // s + 1 was published by the barrier ending step s - 1 and the conv's input is
+                // static, so step s + 1's fragments are read between this step's product groups
+                // (each into the registers its group just released); chunk s + 2 is issued into
+                // the stage chunk s used (read during step s - 1: every wave is past it)
+                for (int cg = 0; cg < kB16Groups; ++cg) {
+#pragma unroll
+                    for (int tap = 0; tap < 9; ++tap) {
+                        const int s = cg * 9 + tap;
+                        const int buf = (cg + tap) & 1;   // = s & 1
+                        if (tap < 7 || cg + 1 < kB16Groups) dma(wl, s + 2, buf);
+                        else if (more) dma(wn, s + 2 - kB16Steps, buf);
+                        const bool nx = tap < 8 || cg + 1 < kB16Groups;   // (scalar)
+                        const int ncg = tap < 8 ? cg : cg + 1;
+                        const char* bn = lds + (buf ^ 1) * kB16Stage;
+                        // per element the chain lo_a hi_b, hi_a hi_b, hi_a lo_b, product-major over
+                        // the 10 tiles (no MFMA waits on the one before)
+#pragma unroll
+                        for (int f = 0; f < 5; ++f)
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j)
+                                acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[f], bh[j], acc[f][j], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (nx) {
+#pragma unroll
+                            for (int f = 0; f < 5; ++f) al[f] = *(const f16x8*)(lds + arow(ncg, f, true));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int f = 0; f < 5; ++f)
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j)
+                                acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f], bh[j], acc[f][j], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (nx) {
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j) bh[j] = *(const f16x8*)(bn + bh0 + j * 2048);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int f = 0; f < 5; ++f)
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j)
+                                acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[f], bl[j], acc[f][j], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (nx) {   // the B reads first: the barrier need only wait for them
+#pragma unroll
+                            for (int j = 0; j < NJ; ++j) bl[j] = *(const f16x8*)(bn + bl0 + j * 2048);
+                            __builtin_amdgcn_sched_barrier(0);
+                            // the hi addresses release the entries: step s + 2's are fetched here, ahead
+                            // of the hi reads, so the wait below covers them and no A read waits on one
+                            int ao[5];
+#pragma unroll
+                            for (int f = 0; f < 5; ++f) ao[f] = arow(ncg, f, false);
+                            if constexpr (!(ABL & 8))
+                                if (tap < 7 || cg + 1 < kB16Groups) entries((tap + 2) % 9);
+                            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                            for (int f = 0; f < 5; ++f) ah[f] = *(const f16x8*)(lds + ao[f]);
+                        }
+                        // chunk s + 2 has landed (this wave's pieces); the barrier publishes it for
+                        // step s + 1's reads, and every wave's reads of chunk s + 1 are complete (its
+                        // stage takes chunk s + 3)
+                        // (the barrier waits for this wave's B reads of chunk s + 1, issued before its
+                        // A reads and the table's: the 5 activation reads may stay in flight -- no DMA
+                        // writes there)
+                        if constexpr (!(ABL & 1)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(5)" ::: "memory");
+                        if constexpr (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+                    }
                 }
             }
 
@@ -530,12 +665,12 @@ __global__ __launch_bounds__(SPLIT ? kB16SplitThreads : kB16Threads, 1) void boa
                 if (t == 1234.5f) xb[tid] = t;
             }
             else if (!(l & 1))
-                bad = b16_epilogue<false, true, (ABL >> 6), false, NJ>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
+                bad = b16_epilogue<false, true, (ABL >> 6), false, NJ, NP>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
             else if (l + 1 < nl)
-                bad = b16_epilogue<true, true, (ABL >> 6), false, NJ>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
+                bad = b16_epilogue<true, true, (ABL >> 6), false, NJ, NP>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
             else if (!SPLIT && a.hout)
-                bad = b16_epilogue<true, false, (ABL >> 6), true, NJ>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
-            else bad = b16_epilogue<true, false, (ABL >> 6), false, NJ>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
+                bad = b16_epilogue<true, false, (ABL >> 6), true, NJ, NP>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
+            else bad = b16_epilogue<true, false, (ABL >> 6), false, NJ, NP>(acc, sc, sh, xr, lds, poff, mg, ng, lane, nb);
             // (a timing ablation's garbage is not posted: the host-mapped stores would be what it times)
             if (ABL == 0 && bad && a.ring_ovf && a.seq)
                 __hip_atomic_store(a.ring_ovf + (a.seq & (kTowerRing - 1)), a.seq, __ATOMIC_RELAXED,
@@ -610,6 +745,8 @@ static hipError_t b16_init()
     for (const void* f : {(const void*)board16_tower<0>, (const void*)board16_tower<0, true>})
 #endif
         if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kB16Lds)) != hipSuccess) return e;
+    for (const void* f : {(const void*)board16_tower<0, false, 1>, (const void*)board16_tower<0, true, 1>})
+        if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kB16Lds)) != hipSuccess) return e;
     int per_cu = 0, dev = 0, cus = 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)board16_tower<0>, kB16Threads, kB16Lds);
     if (e != hipSuccess) return e;
@@ -636,14 +773,15 @@ int board16_split_max()
 hipError_t launch_board16_tower(int NB, const float* wp16, const float* scale16, const float* shift,
                                 const int* out_off, float* x, int B, unsigned* ring_ovf, unsigned seq, hipStream_t st,
                                 const float* hwp, const float* hwv, const float* hsc, const float* hsh, float* hout,
-                                const Board16Split* sp)
+                                const Board16Split* sp, int products)
 {
+    if (products != 1 && products != 3) return hipErrorInvalidValue;
     if (2 * NB > kB16MaxLayers || NB <= 0 || B <= 0) return hipErrorInvalidValue;
     if (hipError_t e = b16_init()) return e;
     const int grid = g_b16_grid;
     Board16Args a{};
     for (int l = 0; l < 2 * NB; ++l) {
-        a.wp[l] = wp16 + (size_t)l * 9 * kB16C * kB16C;
+        a.wp[l] = wp16 + (size_t)l * 9 * kB16C * kB16C / (products == 1 ? 2 : 1);   // (one product: hi halves only)
         a.scale[l] = scale16 + out_off[l];
         a.shift[l] = shift + out_off[l];
     }
@@ -658,10 +796,16 @@ hipError_t launch_board16_tower(int NB, const float* wp16, const float* scale16,
         if (hout || 3 * B > g_b16_cus) return hipErrorInvalidValue;
         a.xbuf = sp->xbuf, a.xflag = sp->xflag, a.epoch = sp->epoch, a.ring = sp->ring, a.diag = sp->diag;
         a.limit = g_tower_wait_us >= 0xffffffffu / 100u ? 0xffffffffu : g_tower_wait_us * 100u;
-        hipLaunchKernelGGL((board16_tower<0, true>), dim3(3 * B), dim3(kB16SplitThreads), kB16Lds, st, a);
+        if (products == 1)
+            hipLaunchKernelGGL((board16_tower<0, true, 1>), dim3(3 * B), dim3(kB16SplitThreads), kB16Lds, st, a);
+        else hipLaunchKernelGGL((board16_tower<0, true>), dim3(3 * B), dim3(kB16SplitThreads), kB16Lds, st, a);
         return hipGetLastError();
     }
     const dim3 g(B < grid ? B : grid);
+    if (products == 1) {   // the one-product fp16 tower (no timing ablations)
+        hipLaunchKernelGGL((board16_tower<0, false, 1>), g, dim3(kB16Threads), kB16Lds, st, a);
+        return hipGetLastError();
+    }
 #ifdef AZG_AB_STUDIES
     switch (g_board_abl) {   // timing ablations (key 51, study build; results invalid while set)
         case 3: hipLaunchKernelGGL(board16_tower<3>, g, dim3(kB16Threads), kB16Lds, st, a); return hipGetLastError();

@@ -247,6 +247,20 @@ int32_t azg_pv_forward_boards_sym(azg_pv* h, const int8_t* boards, const int8_t*
     return run_eval(h, c, stream);
 }
 
+int32_t azg_pv_set_eval_precision(azg_pv* h, int32_t precision)
+{
+    if (!h) return fail("azg_pv_set_eval_precision: null handle");
+    if (precision != AZG_PV_EVAL_EXACT && precision != AZG_PV_EVAL_FP16)
+        return fail("azg_pv_set_eval_precision: unknown precision (0 = exact, 1 = fp16)");
+    if (precision == AZG_PV_EVAL_FP16 && (h->C != 128 || h->NB <= 0 || h->NB > kTowerMaxBlocks))
+        return fail("azg_pv_set_eval_precision: fp16 needs channels == 128 and 1..32 residual blocks "
+                    "(channels 256 and 64 have no one-product tower)");
+    h->eval_precision = precision;
+    return 0;
+}
+
+int32_t azg_pv_get_eval_precision(const azg_pv* h) { return h ? h->eval_precision : -1; }
+
 int32_t azg_pv_profile_enable(azg_pv* h, int32_t enable)
 {
     if (!h) return fail("azg_pv_profile_enable: null handle");
@@ -360,6 +374,7 @@ int32_t azg_pv_recover(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream
     hipStream_t rst = (hipStream_t)stream;
     const bool guard = !ovf && r.h3;
     EvalOpts redo;
+    redo.precision = r.precision;
     redo.per_layer = true;
     redo.fp32_only = ovf;
     redo.guard_seq = guard ? seq : 0u;
@@ -640,7 +655,7 @@ int32_t repack(azg_pv* h, hipStream_t st, float* dgrad_dst, int part)
 
 // The split-fp16 (H3) eval weights of the current parameters (pv_pack.hip pack_h3):
 // allocated on first use, re-packed after every repack.
-int32_t ensure_h3(azg_pv* h, hipStream_t st)
+int32_t ensure_h3(azg_pv* h, hipStream_t st, bool fp16)
 {
     const int C = h->C, nl = 2 * h->NB;
     if (!h->wpack16) {
@@ -660,6 +675,16 @@ int32_t ensure_h3(azg_pv* h, hipStream_t st)
                 "forward: split-fp16 weight pack");
         h->h3_dirty = false;
         ++h->h3_gen;
+    }
+    if (fp16) {   // the hi halves alone, for handles that selected the one-product precision
+        if (!h->wpack1) {
+            AZG_TRY(handle_malloc(h, &h->wpack1, (size_t)nl * 9 * C * C * sizeof(_Float16)), "forward: fp16 weight buffer");
+            h->h1_gen = 0;
+        }
+        if (h->h1_gen != h->h3_gen) {
+            AZG_TRY(launch_pack_h1(h->params, h->conv_off_dev, nl, C, h->h3exp, h->wpack1, st), "forward: fp16 weight pack");
+            h->h1_gen = h->h3_gen;
+        }
     }
     return 0;
 }
@@ -681,6 +706,7 @@ struct TowerPlan {
     int variant = 0;          // see stem_and_tower
     bool h3 = false;          // split-fp16 residual convs
     unsigned seq = 0;         // the launch's number (0: not posted)
+    bool fp16 = false;        // the one-product fp16 precision (variant 14 with one product)
     bool recompute = false;   // azg_pv_recover's rerun: must not wait across workgroups
 };
 
@@ -742,9 +768,10 @@ static int32_t board_tower(azg_pv* h, int images, hipStream_t st, const TowerPla
     // one workgroup per board with the heads fused (sp null), or split with the heads left out
     auto tower16 = [&](float* x, int n, const Board16Split* sp) {
         const bool fused = sp == nullptr;
-        return launch_board16_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, off, x, n, h->ovf_dev, p.seq,
-                                    st, fused ? hp.wpc : nullptr, fused ? hp.wvc : nullptr, fused ? hp.scale : nullptr,
-                                    fused ? hp.shift : nullptr, fused ? h->hbuf : nullptr, sp);
+        return launch_board16_tower(h->NB, (const float*)(p.fp16 ? h->wpack1 : h->wpack16), h->scale16, h->shift, off, x,
+                                    n, h->ovf_dev, p.seq, st, fused ? hp.wpc : nullptr, fused ? hp.wvc : nullptr,
+                                    fused ? hp.scale : nullptr, fused ? hp.shift : nullptr, fused ? h->hbuf : nullptr,
+                                    sp, p.fp16 ? 1 : 3);
     };
     if (!b16) {
         AZG_TRY(launch_board_tower(h->NB, (const float*)h->wpack16, h->scale16, h->shift, off, X, images, h->ovf_dev,
@@ -916,13 +943,17 @@ int32_t forward_eval(azg_pv* h, const EvalCall& c, hipStream_t st, const EvalOpt
     // per-layer, the autotuner's candidates, a recompute -- then computes the same arithmetic
     TowerPlan p;
     p.recompute = o.per_layer;
-    p.h3 = g_tower_h3 != 0 && !o.fp32_only && (C == 128 || C == 256) && h->NB > 0;
+    // a handle in AZG_PV_EVAL_FP16 (checked by the setter: C = 128, 1..32 blocks): the board16
+    // tower with one product, whatever keys 5, 6 and 19 say; a recompute takes the launch's own
+    const int prec = o.precision >= 0 ? o.precision : h->eval_precision;
+    p.fp16 = prec == AZG_PV_EVAL_FP16 && !o.fp32_only;
+    p.h3 = p.fp16 || (g_tower_h3 != 0 && !o.fp32_only && (C == 128 || C == 256) && h->NB > 0);
     if (p.h3)
-        if (int32_t r = ensure_h3(h, st)) return r;
+        if (int32_t r = ensure_h3(h, st, p.fp16)) return r;
     // EVAL_ARITH = 2 at C = 128: the 16x16x32 board tower is the one form of its arithmetic, for
     // every batch and path (it has no cross-workgroup waits: nothing for the breaker to avoid;
     // known defect, ADVICE.md: its split form does wait and still ignores the breaker)
-    const bool k32 = p.h3 && g_tower_h3 == 2 && C == 128 && h->NB <= kTowerMaxBlocks;
+    const bool k32 = p.fp16 || (p.h3 && g_tower_h3 == 2 && C == 128 && h->NB <= kTowerMaxBlocks);
     p.variant = k32 ? 14 : o.per_layer ? 0 : tower_variant(h, c, st, p.h3);
     if (p.variant != 0 && !k32 && h->breaker_until > 0.0) {
         if (now_s() < h->breaker_until) {
@@ -939,7 +970,7 @@ int32_t forward_eval(azg_pv* h, const EvalCall& c, hipStream_t st, const EvalOpt
         p.seq = ++h->seq;
         if (p.seq == 0) p.seq = ++h->seq;   // 0 means "not posted"
         const unsigned slot = p.seq & (kTowerRing - 1);
-        h->launches[slot] = azg_pv::LaunchRec{p.seq, p.h3, c};
+        h->launches[slot] = azg_pv::LaunchRec{p.seq, p.h3, prec, c};
         __atomic_store_n(h->ring_host + slot, 0u, __ATOMIC_RELEASE);
         __atomic_store_n(h->ovf_host + slot, 0u, __ATOMIC_RELEASE);
     }

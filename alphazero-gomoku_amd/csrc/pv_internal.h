@@ -123,7 +123,11 @@ constexpr size_t kB16ImgBytes = 4 * (15 * 15 + 1) * 128;   // pv_board16.hip kB1
 hipError_t launch_board16_tower(int NB, const float* wp16, const float* scale16, const float* shift,
                                 const int* out_off, float* x, int B, unsigned* ring_ovf, unsigned seq, hipStream_t st,
                                 const float* hwp = nullptr, const float* hwv = nullptr, const float* hsc = nullptr,
-                                const float* hsh = nullptr, float* hout = nullptr, const Board16Split* sp = nullptr);
+                                const float* hsh = nullptr, float* hout = nullptr, const Board16Split* sp = nullptr,
+                                int products = 3);   // 1: the one-product fp16 tower, wp16 = pack_h1's hi halves
+// the hi halves of pack_h3's rows ([tap*CG + cg][cout][32] fp16 of w * 2^e), exps as scale_h3_kernel left them
+hipError_t launch_pack_h1(const float* params, const int64_t* offs, int nl, int C, const int* exps, void* wp1,
+                          hipStream_t st);
 
 // the heads' 1x1 projection epilogue: folded eval BN + ReLU (heads_project and the board16 tower)
 __device__ __forceinline__ float head_bn_relu(float d, float s, float h) { return fmaxf(d * s + h, 0.f); }
@@ -182,6 +186,7 @@ struct EvalOpts {
     bool per_layer = false;    // per-layer convs (no cross-workgroup waits); posts no new launch
     bool fp32_only = false;    // fp32 MFMA although split-fp16 is selected
     unsigned guard_seq = 0;    // split-fp16 recompute: a range overflow posts this number
+    int precision = -1;        // the posted launch's eval precision (-1: the handle's current one)
 };
 
 }  // namespace azg
@@ -232,6 +237,11 @@ struct azg_pv {
     std::vector<int> conv_bn_off;   // folded-BN offset of each residual conv (2*NB; build_layout)
     bool h3_dirty = true;
     unsigned h3_gen = 0;   // + 1 per split-fp16 re-pack (the train step's dgrad pack follows it)
+    // one-product fp16 eval precision (azg_pv_set_eval_precision): the hi halves of wpack16's rows,
+    // allocated and packed only once the handle has selected it (ensure_h3)
+    int eval_precision = AZG_PV_EVAL_EXACT;
+    void* wpack1 = nullptr;
+    unsigned h1_gen = 0;   // the h3_gen wpack1 was packed at (0: never)
 
     // eval activations: 3 padded NHWC buffers + head features [B][3][225]
     float* act[3] = {nullptr, nullptr, nullptr};
@@ -254,6 +264,7 @@ struct azg_pv {
     struct LaunchRec {
         unsigned seq = 0;
         bool h3 = false;
+        int precision = AZG_PV_EVAL_EXACT;   // of the launch (the handle may have been switched since)
         azg::EvalCall call;
     };
     std::vector<LaunchRec> launches;
@@ -286,7 +297,7 @@ void free_workspace(azg_pv* h);
 void free_train_workspace(azg_pv* h);
 int32_t ensure_eval_workspace(azg_pv* h, int images, hipStream_t st);
 int32_t repack(azg_pv* h, hipStream_t st, float* dgrad_dst = nullptr, int part = 0);   // dgrad_dst: also pack dgrad weights
-int32_t ensure_h3(azg_pv* h, hipStream_t st);   // split-fp16 packs of the current parameters
+int32_t ensure_h3(azg_pv* h, hipStream_t st, bool fp16 = false);   // split-fp16 packs of the current parameters (fp16: + the hi-only pack)
 int prof_begin(azg_pv* h, int cls, hipStream_t st, int64_t boards = 0);   // returns pair index or -1
 hipError_t prof_harvest(azg_pv* h);
 void prof_end(azg_pv* h, int pair, hipStream_t st);

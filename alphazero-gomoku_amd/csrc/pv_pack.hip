@@ -311,6 +311,34 @@ hipError_t launch_pack_h3(const float* params, const int64_t* offs, int nl, int 
     return hipGetLastError();
 }
 
+// the one-product fp16 eval precision's weights: the hi halves of pack_h3's rows alone, 64-B
+// rows [kc * C + n][32] of fp16(w * 2^e) with the layer's e (exps, after scale_h3_kernel) --
+// the operand the board16 tower's one-product form streams (pv_board16.hip, NP = 1)
+__global__ __launch_bounds__(256) void pack_h1_kernel(const float* __restrict__ params, const int64_t* __restrict__ offs,
+                                                      int C, const int* __restrict__ exps, _Float16* __restrict__ out)
+{
+    const int total = 9 * C * C, cg_n = C / 32;
+    const int l = blockIdx.y;
+    const float* w = params + offs[l];
+    _Float16* o = out + (size_t)l * total;
+    const float sc = ldexpf(1.f, exps[l]);
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int k = idx & 31, n = (idx >> 5) % C, kc = idx / (32 * C);
+        const int tap = kc / cg_n, c2 = (kc - tap * cg_n) * 32 + k;
+        o[idx] = (_Float16)(w[(n * C + c2) * 9 + tap] * sc);
+    }
+}
+
+hipError_t launch_pack_h1(const float* params, const int64_t* offs, int nl, int C, const int* exps, void* wp1,
+                          hipStream_t st)
+{
+    if (nl <= 0) return hipSuccess;
+    int nb = nblk(9 * C * C);
+    nb = nb > 256 ? 256 : nb;
+    hipLaunchKernelGGL(pack_h1_kernel, dim3(nb, nl), dim3(256), 0, st, params, offs, C, exps, (_Float16*)wp1);
+    return hipGetLastError();
+}
+
 // the split-fp16 dgrad packing (key 50): pack_h3's rows for the flipped, transposed taps
 // of pack_convs_kernel's wd (row kc * C + n = cin n, K values = 32 couts of group kc % CG
 // at tap 8 - kc / CG), w * 2^e with the layer's e (exps, after scale_h3_kernel)

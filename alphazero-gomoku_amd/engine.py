@@ -196,6 +196,25 @@ class PolicyValueEngine:
     def tower_diag_clear(self):
         check(self.lib.azg_pv_tower_diag_clear(self.h, _stream(self.device)), self.lib)
 
+    EVAL_PRECISIONS = ("exact", "fp16")   # AZG_PV_EVAL_EXACT, AZG_PV_EVAL_FP16 (include/azg_pv.h)
+
+    @property
+    def eval_precision(self) -> str:
+        return self.EVAL_PRECISIONS[int(self.lib.azg_pv_get_eval_precision(self.h))]
+
+    def set_eval_precision(self, precision: str) -> None:
+        """"exact" (the default: 1e-5 fp32 parity) or "fp16" (one-product fp16 residual
+        convs, for self-play leaf evaluation; C = 128 nets only).  Per handle: another model
+        in the process keeps its own.  ValueError when the value is unknown or the engine
+        has no fp16 form for this net."""
+        if precision not in self.EVAL_PRECISIONS:
+            raise ValueError(f"eval_precision must be one of {self.EVAL_PRECISIONS}, got {precision!r}")
+        if self.lib.azg_pv_set_eval_precision(self.h, self.EVAL_PRECISIONS.index(precision)):
+            err = self.lib.azg_pv_last_error()
+            raise ValueError(f"eval_precision={precision!r} is not supported for a {self.blocks}x{self.channels} "
+                             f"net (supported: 'exact' for every net, 'fp16' for 128 channels and 1..32 blocks): "
+                             f"{err.decode() if err else ''}")
+
     def reattach_grads(self):
         for p, g in zip(self.params, self.grad_views):
             if p.grad is None or p.grad.data_ptr() != g.data_ptr():

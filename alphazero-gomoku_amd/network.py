@@ -350,7 +350,14 @@ class PyTorchModel:
                  n_res_blocks: int = 3,
                  channels: int = 64,
                  lr: float = 1e-3,
-                 weight_decay: float = 1e-4):
+                 weight_decay: float = 1e-4,
+                 eval_precision: str = "exact"):
+        # "exact": every eval forward holds 1e-5 fp32 parity; "fp16": one-product fp16
+        # residual convs (self-play leaf evaluation; 128-channel nets).  Checked before any
+        # device work; never written to checkpoints (save / load keep the reference's format)
+        if eval_precision not in PolicyValueEngine.EVAL_PRECISIONS:
+            raise ValueError(f"eval_precision must be one of {PolicyValueEngine.EVAL_PRECISIONS}, "
+                             f"got {eval_precision!r}")
         self.board_size = board_size
         self.action_size = action_size if action_size is not None else board_size * board_size
         self.device = device or ("cuda" if torch.cuda.is_available() else "cpu")
@@ -367,10 +374,22 @@ class PyTorchModel:
         self.grad_hook = None                           # DP: all-reduce of the flat grads (+ skip word)
         self._losses = None
         self._skips_seen = 0                            # device-skipped steps already accounted for
+        if eval_precision != "exact":
+            self.set_eval_precision(eval_precision)
 
     @property
     def engine(self) -> PolicyValueEngine:
         return self.net.engine
+
+    @property
+    def eval_precision(self) -> str:
+        return self.engine.eval_precision
+
+    def set_eval_precision(self, precision: str) -> None:
+        """The precision of this model's eval forwards (predict, predict_boards, its board
+        evaluators): "exact" or "fp16".  Another model in the process keeps its own; the train
+        step is not affected.  ValueError names what is supported when the engine refuses."""
+        self.engine.set_eval_precision(precision)
 
     # ---------------- inference ----------------
     def predict(self, encoded_states: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:

@@ -22,7 +22,7 @@ from mcts.native_mcts import NativeMCTS
 
 class AlphaPlayer:
     def __init__(self, rules="gomoku", board_size=15, n_simulations=5000, c_puct=1.0, model_path=None,
-                 nn_model=None, mcts_kwargs=None, mcts_class=None, leaf_symmetry=None):
+                 nn_model=None, mcts_kwargs=None, mcts_class=None, leaf_symmetry=None, eval_precision=None):
         if nn_model is None:
             from network import PyTorchModel
             nn_model = PyTorchModel
@@ -38,6 +38,10 @@ class AlphaPlayer:
         else:
             print("[PlayerAlpha] WARNING: no model given, using random weights")
         self.net.net.eval()
+        # eval_precision (None, "exact" or "fp16"): the loaded model's eval precision
+        # (PyTorchModel.set_eval_precision); None leaves the model's own
+        if eval_precision is not None:
+            self.net.set_eval_precision(eval_precision)
         if self.rules != "gomoku":
             raise ValueError(f"Unsupported rules: {self.rules}. Only 'gomoku' is supported.")
         self.game_class = Gomoku

@@ -147,7 +147,7 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     dirichlet_epsilon: float = 0.25, dirichlet_n_moves: int = 30, n_res_blocks: int = 3,
                     channels: int = 64, device: Optional[str] = None, max_moves: Optional[int] = None,
                     device_buffer: bool = False, leaf_symmetry=None, eval_symmetry=None,
-                    **reference_worker_kwargs):
+                    selfplay_precision: Optional[str] = None, **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -160,7 +160,14 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     leaf_symmetry / eval_symmetry (None, an int 0..7, "random" or "mean8"): evaluate the
     leaves of self-play, respectively of both gating models, under board symmetries
     (network.SymmetricModel; the transform runs inside the forward's kernels).  None, the
-    default, is the loop without them, bit for bit."""
+    default, is the loop without them, bit for bit.
+
+    selfplay_precision ("exact", "fp16" or None = "exact"): the candidate model's eval
+    precision (PyTorchModel.set_eval_precision) during the self-play phase of each
+    iteration only; it is back at "exact" before the train steps and before gating,
+    whatever self-play raises.  Gating always compares exact forwards."""
+    if selfplay_precision not in (None, "exact", "fp16"):
+        raise ValueError(f"selfplay_precision must be None, 'exact' or 'fp16', got {selfplay_precision!r}")
     r, w, _, dev = D.init_from_env()
     device = device or str(dev)
     main = r == 0
@@ -198,10 +205,16 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                   f"ranks={w}) {datetime.now():%Y-%m-%d %H:%M:%S} ===")
         n_local = len(D.shard(games_per_iteration))
         sp_model = model_candidate if leaf_symmetry is None else model_candidate.symmetric(leaf_symmetry)
-        examples, winners, drv = selfplay_games(sp_model, GameClass, n_local, n_simulations, cpuct, temp_fn,
-                                                dirichlet_alpha, dirichlet_epsilon, dirichlet_n_moves,
-                                                max_moves=max_moves, board_size=board_size,
-                                                use_symmetries=host_symmetries)
+        try:
+            if selfplay_precision not in (None, "exact"):
+                model_candidate.set_eval_precision(selfplay_precision)
+            examples, winners, drv = selfplay_games(sp_model, GameClass, n_local, n_simulations, cpuct, temp_fn,
+                                                    dirichlet_alpha, dirichlet_epsilon, dirichlet_n_moves,
+                                                    max_moves=max_moves, board_size=board_size,
+                                                    use_symmetries=host_symmetries)
+        finally:
+            if selfplay_precision not in (None, "exact"):
+                model_candidate.set_eval_precision("exact")
         if device_buffer:
             buffer.add_positions(examples)
         else:

@@ -132,6 +132,26 @@ int32_t azg_pv_forward_boards_sym(azg_pv* h, const int8_t* boards, const int8_t*
                                   const int8_t* syms, int32_t mode, int32_t batch,
                                   float* probs, float* values, float* priors, void* stream);
 
+/* Eval precision of ONE handle (not a tuning key: those are process-wide).
+ * AZG_PV_EVAL_EXACT (the default): the eval forward runs the arithmetic key 19 selects, all
+ * of which hold 1e-5 parity with the fp32 reference.
+ * AZG_PV_EVAL_FP16: the residual convs run on fp16 operands with ONE product per MFMA step
+ * (the 16x16x32 board tower without the split's two correction products): conv operands are
+ * rounded once to fp16 (the weights times the layer's 2^e, the activations under the
+ * activation-exponent fold), accumulated in fp32; the trunk, the BN epilogue, the stem and
+ * the heads stay fp32.  Outputs deviate from the fp32 reference by about 1e-3 on values and
+ * 1e-4 on probabilities: meant for self-play leaf evaluation, not for gating or anything
+ * compared with the reference.  In this mode every azg_pv_forward* entry point, every batch
+ * size and every launch form computes the same MFMA sequence per element, whatever keys 5, 6
+ * and 19 say; an activation beyond fp16's range is still posted and azg_pv_recover recomputes
+ * it in fp32.  azg_pv_recover reruns a posted launch in the precision it was launched with.
+ * set: returns nonzero (azg_pv_last_error) on a null handle, an unknown value, or FP16 on a
+ * net it has no kernel for -- it needs channels == 128 and 1..32 blocks (channels 256 and
+ * 64 have no one-product form); checked before any device call.  get: -1 on a null handle. */
+enum { AZG_PV_EVAL_EXACT = 0, AZG_PV_EVAL_FP16 = 1 };
+int32_t azg_pv_set_eval_precision(azg_pv* h, int32_t precision);
+int32_t azg_pv_get_eval_precision(const azg_pv* h);
+
 /* Train-mode forward + loss + backward on the local batch (reference
  * network.py:213-222).  Writes d(loss)/d(param) into the bound grad buffer
  * (overwrites: zero_grad semantics), updates BN running stats (momentum 0.1,

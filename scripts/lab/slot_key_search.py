@@ -10,6 +10,15 @@ fragment's first row shifted by the tap (any residue).  Conflict-free iff the 16
     python scripts/lab/slot_key_search.py
 prints the formula keys that are conflict-free for every shift b (key = row & 6 among them,
 the one the tower uses) and the first solutions of a brute-force search over period-16 keys.
+
+    python scripts/lab/slot_key_search.py --weights
+searches the stage layout of the one-product fp16 tower's weight chunks instead: 128 rows of
+64 B (the hi halves only), so FOUR consecutive rows make one 256-B bank window and a row has
+4 slots.  A B fragment reads rows 16 j + {0..15} (no tap shift: b = 0) at slot kb, in the same
+lane groups: rows {0-3, 12-15} at slot kb with rows {4-11} at slot kb ^ 1.  Conflict-free iff
+the 16 lanes hit 16 distinct (row & 3, physical slot) pairs, physical slot = s ^ key(row).
+The LDS-DMA writes 1 KiB per wave contiguously (16 whole rows), so any key is served by the
+source address of a lane (its slot ^ key(row)): the pack stays plain [row][32 halves].
 """
 S = [1 if 4 <= i <= 11 else 0 for i in range(16)]
 
@@ -26,7 +35,37 @@ def conflict_free(key, P):
     return True
 
 
+def weights_conflict_free(key):
+    """key: 16 values 0..3, one per row of a fragment's 16 weight rows (64-B rows)."""
+    for kb in range(4):
+        for grp in (0, 1):   # lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (+ 32: kb + 2)
+            seen = set()
+            for i in range(16):
+                s = kb ^ (S[i] ^ grp)      # group 1 reads rows 4-11 at kb, the others at kb ^ 1
+                u = 4 * (i & 3) + (s ^ key[i])
+                if u in seen:
+                    return False
+                seen.add(u)
+    return True
+
+
+def weights_main():
+    import itertools
+    print("no key (plain 64-B rows):", weights_conflict_free([0] * 16))
+    print("key = row quad (row >> 2) & 3:", weights_conflict_free([(i >> 2) & 3 for i in range(16)]))
+    print("key = (row >> 1) & 3:", weights_conflict_free([(i >> 1) & 3 for i in range(16)]))
+    good = [q for q in itertools.product(range(4), repeat=4)
+            if weights_conflict_free([q[(i >> 2) & 3] for i in range(16)])]
+    print("conflict-free keys that depend on the row quad only, key(quad 0..3):", good)
+    tower = [((i >> 2) & 3) ^ ((i >> 1) & 2) for i in range(16)]
+    print("pv_board16.hip b16_wkey = ((row >> 2) & 3) ^ ((row >> 1) & 2) -> per quad",
+          [tower[4 * q] for q in range(4)], ":", weights_conflict_free(tower))
+
+
 def main():
+    import sys
+    if "--weights" in sys.argv:
+        return weights_main()
     P = 32
     good = []
     for a in range(8):
