@@ -25,6 +25,27 @@ class TowerFault(RuntimeError):
     """A persistent-tower forward computed on stale inputs and could not be recomputed."""
 
 
+# fields of a score record, in order (include/azg_pv.h AZG_PV_SCORE_*)
+SCORE_FIELDS = ("kl", "sq", "entropy", "top1", "p_best", "v_agree", "decided", "target_mass")
+
+
+def score_summary(sums, n) -> dict:
+    """Means over n boards from the summed score records (PolicyValueEngine.score_outputs),
+    in float64.  The first three keys are train_batch's: policy_loss is
+    KLDivLoss(batchmean), value_loss MSELoss.  value_sign_agreement is taken over the
+    decided boards (z != 0) only; with none it is 0."""
+    s = [float(v) for v in sums]
+    if len(s) != len(SCORE_FIELDS):
+        raise ValueError(f"score_summary: {len(SCORE_FIELDS)} sums expected, got {len(s)}")
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"score_summary: n must be >= 1, got {n}")
+    policy, value = s[0] / n, s[1] / n
+    return {"policy_loss": policy, "value_loss": value, "total_loss": policy + value,
+            "policy_entropy": s[2] / n, "policy_top1": s[3] / n, "target_move_prob": s[4] / n,
+            "value_sign_agreement": s[5] / max(s[6], 1.0), "target_mass": s[7] / n, "n": n}
+
+
 class PolicyValueEngine:
     MEAN8_MAX_BOARDS = 2048   # azg_pv_forward_boards_sym mode 1: boards per call (8 images each)
 
@@ -281,6 +302,34 @@ class PolicyValueEngine:
         check(self.lib.azg_pv_train_apply(self.h, ptr(exp_avg), ptr(exp_avg_sq), int(step), float(lr),
                                           float(beta1), float(beta2), float(eps), float(wd), float(max_norm),
                                           ptr(total_norm), _stream(self.device)), self.lib)
+
+    def score_outputs(self, logits, values, pis, zs):
+        """Score eval-forward outputs against targets on the device (include/azg_pv.h
+        azg_pv_score_outputs; nothing but the results is written).  logits [B,225] as
+        forward(want_logits=True) returns them, values [B] or [B,1], pis [B,225], zs [B] or
+        [B,1]: contiguous float32 tensors on this engine's device.  Returns (per_board
+        [B,8] float32 in SCORE_FIELDS order, sums [8] float64), device tensors, queued on
+        the current stream.  Passing another model's probs and values as pis and zs gives
+        the drift between two models.  ValueError on a wrong shape, dtype or device."""
+        B = int(logits.shape[0]) if torch.is_tensor(logits) and logits.dim() == 2 else 0
+        if B < 1:
+            raise ValueError("score_outputs: logits must be a [B,225] tensor with B >= 1")
+        for name, t, shapes in (("logits", logits, ((B, 225),)), ("values", values, ((B,), (B, 1))),
+                                ("pis", pis, ((B, 225),)), ("zs", zs, ((B,), (B, 1)))):
+            if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
+                raise ValueError(f"score_outputs: {name} must be a tensor of shape {' or '.join(map(str, shapes))}, "
+                                 f"got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"score_outputs: {name} must be contiguous float32, got {t.dtype}")
+            if t.device != logits.device or t.device.type != "cuda" or \
+                    (self.device.index is not None and t.device != self.device):
+                raise ValueError(f"score_outputs: {name} is on {t.device}, the engine on {self.device}")
+        dev = logits.device
+        per_board = torch.empty((B, len(SCORE_FIELDS)), dtype=torch.float32, device=dev)
+        sums = torch.empty(len(SCORE_FIELDS), dtype=torch.float64, device=dev)
+        check(self.lib.azg_pv_score_outputs(ptr(logits), ptr(values), ptr(pis), ptr(zs), B, ptr(per_board), ptr(sums),
+                                            _stream(dev)), self.lib)
+        return per_board, sums
 
     # -- instrumentation ----------------------------------------------------
     DEBUG_BUFFERS = {"z0": 0, "a0": 1, "z1": 2, "h": 3, "z2": 4, "xo": 5, "gX": 6, "DZ": 7, "DH": 8, "GR": 9, "snap": 10}

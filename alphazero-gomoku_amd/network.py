@@ -10,7 +10,9 @@ Same public surface as the reference (network.py:9-265):
     ``load``, ``make_batch_from_states`` and the attributes ``.net``, ``.optimizer``,
     ``.board_size``, ``.action_size``, ``.device``; plus ``policy_value`` /
     ``train_step`` aliases named by the north star, and device-resident variants
-    (``predict_device``) for the batched self-play driver.
+    (``predict_device``) for the batched self-play driver, and ``score_batch`` /
+    ``score_batch_device``: the train step's two losses and policy / value metrics of a
+    batch from the eval forward, changing nothing.
 
 Differences, by design: the device must be a HIP GPU (there is no CPU path: the
 reference's CPU fallback, network.py:152, raises here) and the board must be 15x15.
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from engine import PolicyValueEngine
+from engine import PolicyValueEngine, score_summary
 
 MEAN8_MAX_BOARDS = PolicyValueEngine.MEAN8_MAX_BOARDS   # boards per mean-of-8 forward (8 images each)
 _N = 15
@@ -557,6 +559,80 @@ class PyTorchModel:
 
     train_step = train_batch
 
+    # ---------------- scoring (no training) ----------------
+    def score_batch(self, states: np.ndarray, target_pis: np.ndarray, target_vs: np.ndarray,
+                    per_board: bool = False, max_batch: int = 4096):
+        """Held-out loss and policy / value metrics of a batch, changing nothing: the host-
+        array form of score_batch_device (arrays as train_batch takes them).  With
+        per_board=True the records come back as a numpy [B,8] array."""
+        sums, records = self.score_sums(states, target_pis, target_vs, per_board=per_board, max_batch=max_batch)
+        summary = score_summary(sums, len(states))
+        return (summary, records) if per_board else summary
+
+    def score_sums(self, states, target_pis, target_vs, per_board: bool = False, max_batch: int = 4096):
+        """score_sums_device on host arrays (the records, if asked for, as numpy)."""
+        dev = self.engine.device
+        s = torch.from_numpy(np.ascontiguousarray(states, dtype=np.float32)).to(dev)
+        t = torch.from_numpy(np.ascontiguousarray(target_pis, dtype=np.float32)).to(dev)
+        z = torch.from_numpy(np.ascontiguousarray(target_vs, dtype=np.float32).reshape(-1, 1)).to(dev)
+        sums, records = self.score_sums_device(s, t, z, per_board=per_board, max_batch=max_batch)
+        return sums, (records.cpu().numpy() if per_board else None)
+
+    def score_batch_device(self, s: torch.Tensor, t: torch.Tensor, z: torch.Tensor, per_board: bool = False,
+                           max_batch: int = 4096):
+        """Score s [B,3,15,15] against targets t [B,225], z [B] or [B,1] (device tensors):
+        the eval forward (BN running stats, this model's eval precision) with logits, then
+        the scoring kernels (engine.score_outputs), in chunks of at most max_batch boards.
+        Returns engine.score_summary's dict -- policy_loss (KLDiv batchmean), value_loss
+        (MSE) and total_loss as train_batch names them, policy_entropy, policy_top1,
+        target_move_prob, value_sign_agreement, target_mass, n -- and with per_board=True
+        also the [B,8] records (engine.SCORE_FIELDS) as a device tensor.
+
+        Only the sums reach the host (one copy per chunk, added in float64 in chunk order).
+        The module's train / eval flag, parameters, gradients, BN statistics and counters
+        and the optimizer are untouched.  Each chunk is settled as predict settles its
+        forward: a posted launch is recomputed and its chunk scored again.
+        A SymmetricModel forwards both score methods to its model unchanged: scoring is not
+        leaf evaluation and applies no symmetry."""
+        sums, records = self.score_sums_device(s, t, z, per_board=per_board, max_batch=max_batch)
+        summary = score_summary(sums, int(s.shape[0]))
+        return (summary, records) if per_board else summary
+
+    def score_sums_device(self, s: torch.Tensor, t: torch.Tensor, z: torch.Tensor, per_board: bool = False,
+                          max_batch: int = 4096):
+        """score_batch_device's raw result, for callers that add up several calls
+        (train.score_buffer): (the 8 field sums as a float64 numpy array, the [B,8] device
+        records or None)."""
+        eng = self.engine
+        if max_batch < 1:
+            raise ValueError(f"max_batch must be >= 1, got {max_batch}")
+        s = s.to(eng.device, torch.float32).contiguous()   # alive until every chunk is settled
+        t = t.to(eng.device, torch.float32).contiguous()
+        z = z.to(eng.device, torch.float32).contiguous().reshape(-1)
+        B = int(s.shape[0])
+        if B < 1 or tuple(s.shape[1:]) != (3, _N, _N) or tuple(t.shape) != (B, _N * _N) or z.numel() != B:
+            raise ValueError(f"score: states [B,3,{_N},{_N}], pis [B,{_N * _N}] and zs [B] with B >= 1 expected, got "
+                             f"{tuple(s.shape)}, {tuple(t.shape)}, {tuple(z.shape)}")
+        total = np.zeros(8, dtype=np.float64)
+        records = []
+        for lo in range(0, B, max_batch):
+            hi = min(B, lo + max_batch)
+            x = s[lo:hi]
+            _, values, logits = eng.forward(x, want_logits=True)
+            seq = eng.last_seq()
+            rec, sums = eng.score_outputs(logits, values, t[lo:hi], z[lo:hi])
+            host = sums.cpu().numpy()
+            if eng.recover(seq):   # a posted forward left invalid logits: recomputed in place, scored again
+                rec, sums = eng.score_outputs(logits, values, t[lo:hi], z[lo:hi])
+                host = sums.cpu().numpy()
+            eng.check_orphans()
+            total += host
+            if per_board:
+                records.append(rec)
+        if not per_board:
+            return total, None
+        return total, records[0] if len(records) == 1 else torch.cat(records)
+
     # ---------------- checkpoints ----------------
     def save(self, path: str) -> None:
         """network.py:240-248 format: {"net", "opt", "board_size", "action_size"}."""
@@ -595,7 +671,8 @@ class SymmetricModel:
     evaluation) or "mean8" (the mean over all 8 images: exactly equivariant, 8x the cost).
     Self-play, gating and the players only call ``board_evaluator`` / ``predict``, so the
     proxy drops into selfplay_games, NativeSelfPlay, NativeEval, evaluate_models and
-    NativeMCTS unchanged; everything else (net, engine, save, ...) is the model's.
+    NativeMCTS unchanged; everything else (net, engine, save, ...) is the model's --
+    score_batch and score_batch_device among them: scoring applies no symmetry.
 
     seed: evaluator number k of a seeded proxy draws from Generator([seed, k]); predict
     draws from Generator(seed).  A position is evaluated once per tree node, so its

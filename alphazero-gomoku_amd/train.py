@@ -11,7 +11,10 @@ semantics (reference train.py:575-845), running on the HIP engine:
     pickle (train.py:829-840);
   * under torchrun (one process per GPU): games shard across ranks, the train
     step is data-parallel with one RCCL all-reduce of the flat gradient,
-    evaluation wins are summed across ranks, BN stats averaged per iteration.
+    evaluation wins are summed across ranks, BN stats averaged per iteration;
+  * beyond the reference: ``score_buffer`` and ``train_alphazero(score_new_games=True,
+    history=[...])`` report eval-mode losses and policy metrics of a buffer / of the
+    iteration's fresh games without training on them (PyTorchModel.score_batch).
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import torch
 import distributed as D
 from games.gomoku import Gomoku as GameClass
 from mcts.new_mcts_alpha import MCTS
-from engine import TowerFault
+from engine import TowerFault, score_summary
 from network import PyTorchModel
 from selfplay import (BatchedSelfPlay, ReplayBuffer, load_replay_buffer, play_game_and_collect,  # noqa: F401
                       sample_action_from_pi, save_replay_buffer, selfplay_games, softmax_temperature)
@@ -138,6 +141,50 @@ def _new_model(board_size, action_size, device, blocks, channels, like: Optional
     return m
 
 
+def _stack_examples(examples):
+    states, pis, zs = zip(*examples)
+    return (np.stack(states, axis=0).astype(np.float32), np.stack(pis, axis=0).astype(np.float32),
+            np.array(zs, dtype=np.float32).reshape(-1, 1))
+
+
+def score_buffer(model, buffer, batch_size: int = 512, max_examples: Optional[int] = None) -> dict:
+    """Eval-mode loss and policy / value metrics (PyTorchModel.score_batch's dict) of a
+    whole replay buffer, or of its first max_examples examples, training nothing.  A
+    replay.DeviceReplayBuffer is swept in image-id order through its gather kernel and
+    score_batch_device: nothing goes to the host but the sums.  A host ReplayBuffer is
+    swept in deque order.  Both orders are the same examples (image i of the device
+    buffer is element i of the deque), the batches' sums are added in float64 in sweep
+    order, and no RNG is consumed."""
+    n = len(buffer) if max_examples is None else min(len(buffer), int(max_examples))
+    if n < 1 or batch_size < 1:
+        raise ValueError(f"score_buffer: nothing to score (examples={n}, batch_size={batch_size})")
+    total = np.zeros(8, dtype=np.float64)
+    on_device = hasattr(buffer, "add_positions")   # replay.DeviceReplayBuffer
+    examples = None if on_device else iter(buffer.buffer)
+    for lo in range(0, n, batch_size):
+        hi = min(n, lo + batch_size)
+        if on_device:
+            s, p, z = buffer.sample(hi - lo, ids=range(lo, hi))
+            sums, _ = model.score_sums_device(s, p, z, max_batch=batch_size)
+        else:
+            s, p, z = _stack_examples([next(examples) for _ in range(hi - lo)])
+            sums, _ = model.score_sums(s, p, z, max_batch=batch_size)
+        total += sums
+    return score_summary(total, n)
+
+
+def _score_new_games(model, examples, limit: int) -> Optional[dict]:
+    examples = examples[:max(0, int(limit))]
+    return model.score_batch(*_stack_examples(examples)) if examples else None
+
+
+def _score_line(tag: str, d: Optional[dict]) -> str:
+    if d is None:
+        return f"  new games {tag}: no examples on this rank"
+    return (f"  new games {tag}: n={d['n']} policy_loss={d['policy_loss']:.6f} value_loss={d['value_loss']:.6f} "
+            f"total_loss={d['total_loss']:.6f} policy_top1={d['policy_top1']:.4f}")
+
+
 def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterations: int = 5,
                     games_per_iteration: int = 8, n_simulations: int = 50, buffer_size: int = 10000,
                     batch_size: int = 128, epochs_per_iter: int = 2, temp_threshold: int = 8, eval_games: int = 12,
@@ -147,7 +194,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     dirichlet_epsilon: float = 0.25, dirichlet_n_moves: int = 30, n_res_blocks: int = 3,
                     channels: int = 64, device: Optional[str] = None, max_moves: Optional[int] = None,
                     device_buffer: bool = False, leaf_symmetry=None, eval_symmetry=None,
-                    selfplay_precision: Optional[str] = None, **reference_worker_kwargs):
+                    selfplay_precision: Optional[str] = None, score_new_games: bool = False,
+                    score_max_examples: int = 4096, history: Optional[list] = None, **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -165,7 +213,18 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     selfplay_precision ("exact", "fp16" or None = "exact"): the candidate model's eval
     precision (PyTorchModel.set_eval_precision) during the self-play phase of each
     iteration only; it is back at "exact" before the train steps and before gating,
-    whatever self-play raises.  Gating always compares exact forwards."""
+    whatever self-play raises.  Gating always compares exact forwards.
+
+    score_new_games=True: the candidate scores the iteration's fresh self-play examples
+    (the first score_max_examples of them on this rank; PyTorchModel.score_batch: eval-mode
+    losses and policy metrics, nothing trained) twice -- before they enter the buffer, when
+    the net has never trained on them, and again after the iteration's train steps and BN
+    sync -- both in "exact" precision, and rank 0 prints both.  history (a list): one dict
+    per iteration is appended, {"iteration", "new_games_before", "new_games_after",
+    "last_train_loss"} (the score dicts are None without score_new_games or without local
+    examples; last_train_loss is None when the iteration did not train).  Scoring consumes
+    no RNG and changes nothing about the buffer, the steps or gating; with the defaults no
+    scoring call is made."""
     if selfplay_precision not in (None, "exact", "fp16"):
         raise ValueError(f"selfplay_precision must be None, 'exact' or 'fp16', got {selfplay_precision!r}")
     r, w, _, dev = D.init_from_env()
@@ -215,6 +274,11 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         finally:
             if selfplay_precision not in (None, "exact"):
                 model_candidate.set_eval_precision("exact")
+        score_before = score_after = None
+        if score_new_games:   # before the examples enter the buffer: the net has never trained on them
+            score_before = _score_new_games(model_candidate, examples, score_max_examples)
+            if main:
+                print(_score_line("before training", score_before))
         if device_buffer:
             buffer.add_positions(examples)
         else:
@@ -226,8 +290,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                   f"max batch {drv.max_batch})")
 
         n_batches = D.allreduce_min_int(len(buffer) // batch_size, model_candidate.engine.device)
+        loss_info = None
         if n_batches >= 1:
-            loss_info = None
             for epoch in range(epochs_per_iter):
                 te = time.time()
                 for _ in range(n_batches):
@@ -241,6 +305,13 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             D.sync_bn_stats(model_candidate)
         elif main:
             print(f"not enough samples (buffer={len(buffer)}, need {batch_size}): skip training")
+        if score_new_games:
+            score_after = _score_new_games(model_candidate, examples, score_max_examples)
+            if main:
+                print(_score_line("after training", score_after))
+        if history is not None:
+            history.append({"iteration": it, "new_games_before": score_before, "new_games_after": score_after,
+                            "last_train_loss": loss_info})
 
         te = time.time()
         try:

@@ -201,6 +201,49 @@ int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, const float
                              const int64_t* ids, int32_t batch,
                              float* x, float* pi_out, float* z_out, void* stream);
 
+/* Score eval-forward outputs against targets without a train step (handle-free): the two
+ * loss terms of the reference's train_batch -- KLDivLoss(batchmean) on log_softmax(logits)
+ * and MSELoss on the value, network.py:162-163,216-219 -- per board and summed, plus policy
+ * and value metrics.  Nothing is written but per_board and sums.
+ * Inputs (device fp32): logits [batch][225], exactly what azg_pv_forward writes to its
+ * `logits` output; values [batch]; pis [batch][225]; zs [batch].  Targets are just device
+ * tensors: passing ANOTHER model's probs and values as pis and zs gives the policy drift
+ * (KL) and value distance between two models.
+ * per_board [batch][AZG_PV_SCORE_FIELDS]: one record per board, from that board's inputs
+ * only (one wavefront per board), with lp_j = (l_j - max) - logf(sum_j expf(l_j - max)),
+ * t = pis, v = values, z = zs:
+ *   0 KL           sum over t_j > 0 of t_j * (logf(t_j) - lp_j)   (the train step's term)
+ *   1 SQ           (v - z)^2
+ *   2 ENTROPY      -sum_j expf(lp_j) * lp_j   (from lp: an underflowed probability adds 0)
+ *   3 TOP1         1.0 if argmax_j l_j == argmax_j t_j, else 0.0 (both argmaxes take the
+ *                  lowest index among equal maxima)
+ *   4 P_BEST       expf(lp_j*), j* = argmax_j t_j
+ *   5 V_AGREE      1.0 if v * z > 0, else 0.0
+ *   6 DECIDED      1.0 if z != 0, else 0.0
+ *   7 TARGET_MASS  sum_j t_j
+ * sums [AZG_PV_SCORE_FIELDS] (device fp64, or NULL to skip): the records summed in fp64 in
+ * an order that depends on batch alone (one workgroup, thread i adds records i, i + 256,
+ * ... in increasing order, then a fixed tree; no atomics), so equal records give equal
+ * sums bit for bit.  Means are the caller's: policy loss = sums[0] / batch, value loss =
+ * sums[1] / batch, value sign agreement = sums[5] / sums[6].
+ * Arguments are checked before any device call: a null logits, values, pis, zs or
+ * per_board, or batch < 1, returns nonzero and azg_pv_last_error names the argument.  Two
+ * launches, asynchronous on `stream`, no allocation. */
+enum {
+    AZG_PV_SCORE_KL = 0,
+    AZG_PV_SCORE_SQ = 1,
+    AZG_PV_SCORE_ENTROPY = 2,
+    AZG_PV_SCORE_TOP1 = 3,
+    AZG_PV_SCORE_P_BEST = 4,
+    AZG_PV_SCORE_V_AGREE = 5,
+    AZG_PV_SCORE_DECIDED = 6,
+    AZG_PV_SCORE_TARGET_MASS = 7,
+    AZG_PV_SCORE_FIELDS = 8
+};
+int32_t azg_pv_score_outputs(const float* logits, const float* values, const float* pis, const float* zs,
+                             int32_t batch, float* per_board /* [batch][8] */, double* sums /* [8] or NULL */,
+                             void* stream);
+
 /* Kernel-class event timing (bench / roofline instrumentation).  When enabled,
  * every launch of a profiled class is bracketed by hipEvents on the stream it is
  * launched on; azg_pv_profile_read synchronises those events and returns the
