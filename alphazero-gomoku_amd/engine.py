@@ -123,8 +123,11 @@ class PolicyValueEngine:
     # -- housekeeping -------------------------------------------------------
     def _versions(self):
         # nn.Parameter keeps its own version counter after `p.data = view`, so sum them;
-        # BN buffers ARE views of flat_bn and share its counter.
-        return (self.flat_params._version, self.flat_bn._version, sum(p._version for p in self.params))
+        # BN buffers ARE views of flat_bn and share its counter; the num_batches_tracked
+        # buffers are views of flat_nbt (a counter written alone, e.g. bn.num_batches_tracked
+        # .zero_(), must refresh the copy a skipped train step restores).
+        return (self.flat_params._version, self.flat_bn._version, self.flat_nbt._version,
+                sum(p._version for p in self.params))
 
     def sync_dirty(self):
         """Parameters or BN stats were modified in place through torch (load_state_dict,

@@ -157,12 +157,66 @@ def param_count(blocks: int, channels: int, board: int = 15) -> int:
     return stem + tower + pol + val
 
 
-def masked_forward_fp64(net: nn.Module, x, masks: dict):
+def bn_update_fp64(z, rm0, rv0, momentum: float = 0.1):
+    """(running_mean, running_var) in float64 after ONE train-mode BatchNorm update
+    (network.py:12-25) from the pre-BN tensor z (NCHW, or [N, C] rows) and the old
+    stats: the batch mean and the UNBIASED variance over all N rows (N = B * 225 for a
+    15x15 board), each weighted `momentum` against the old value."""
+    z = np.asarray(z, dtype=np.float64)
+    rows = np.moveaxis(z, 1, -1).reshape(-1, z.shape[1])
+    mean = rows.mean(axis=0)
+    var = ((rows - mean) ** 2).sum(axis=0) / (rows.shape[0] - 1)
+    rm0, rv0 = np.asarray(rm0, dtype=np.float64), np.asarray(rv0, dtype=np.float64)
+    return (1.0 - momentum) * rm0 + momentum * mean, (1.0 - momentum) * rv0 + momentum * var
+
+
+def bn_stat_tolerance(want64, dev32: float):
+    """Per stored element, the gate of a running stat against its fp64 value:
+    2^-23 |want64| (the stored fp32 value's own rounding and one more on the way) + 4 x
+    dev32, the largest deviation over that tensor of a plain float32 computation of the
+    same update from the fp64 one (never the error of the code under test)."""
+    return 2.0 ** -23 * np.abs(np.asarray(want64, dtype=np.float64)) + 4.0 * float(dev32)
+
+
+def bn_layer_names(blocks: int) -> list:
+    """State-dict prefixes of the BatchNorm layers in module order (the order of the
+    engine's flat stats and counters)."""
+    names = ["bn"]
+    for i in range(blocks):
+        names += [f"res_blocks.{i}.bn1", f"res_blocks.{i}.bn2"]
+    return names + ["policy_bn", "value_bn"]
+
+
+def randomized_bn_state(state: dict, blocks: int, seed: int) -> dict:
+    """A copy of `state` whose BN buffers are distinct and non-default in every layer and
+    channel: running_mean uniform in (-0.5, 0.5), running_var uniform in (0.5, 1.5),
+    num_batches_tracked = 3 + layer index.  (The constructor's 0 / 1 / 0 hides a read of
+    the old value at the wrong channel or layer.)"""
+    rng = np.random.default_rng(seed)
+    out = dict(state)
+    for i, n in enumerate(bn_layer_names(blocks)):
+        c = np.asarray(state[f"{n}.running_mean"]).shape[0]
+        out[f"{n}.running_mean"] = rng.uniform(-0.5, 0.5, c).astype(np.float32)
+        out[f"{n}.running_var"] = rng.uniform(0.5, 1.5, c).astype(np.float32)
+        out[f"{n}.num_batches_tracked"] = np.asarray(3 + i, dtype=np.int64)
+    return out
+
+
+def bn_buffers(net: nn.Module) -> dict:
+    """{state_dict key: ndarray} of every running_mean / running_var / num_batches_tracked."""
+    return {k: v.detach().cpu().numpy().copy() for k, v in net.state_dict().items()
+            if "running_" in k or "num_batches_tracked" in k}
+
+
+def masked_forward_fp64(net: nn.Module, x, masks: dict, return_buffers: bool = False, dtype=torch.float64):
     """Train-mode forward in float64 where every ReLU is replaced by the caller's
     0/1 mask (e.g. the GPU's own forward).  Returns (logits, value, pre) where
     pre[name] is the fp64 PRE-activation of the masked ReLU `name` (a0, h{i}, xo{i},
-    fp, fv, hv) given the masks upstream of it -- what a flipped mask is judged by."""
-    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+    fp, fv, hv) given the masks upstream of it -- what a flipped mask is judged by.
+    return_buffers: also the net's BN buffers after the forward (bn_buffers).  dtype: the
+    arithmetic of the run (the net must be of that dtype); torch.float32 gives the fp32
+    reference that the BN-stat tolerances are measured with."""
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype)
     mk = {k: t(v) for k, v in masks.items()}
     pre = {}
     z = net.bn(net.conv(t(x)))
@@ -184,10 +238,13 @@ def masked_forward_fp64(net: nn.Module, x, masks: dict):
     z = net.value_fc1(z * mk["fv"])
     pre["hv"] = z
     value = torch.tanh(net.value_fc2(z * mk["hv"]))
+    if return_buffers:
+        return logits, value, pre, bn_buffers(net)
     return logits, value, pre
 
 
-def masked_grads_fp64(state: dict, blocks: int, channels: int, x, pi, z, masks: dict, return_pre: bool = False):
+def masked_grads_fp64(state: dict, blocks: int, channels: int, x, pi, z, masks: dict, return_pre: bool = False,
+                      return_buffers: bool = False, dtype=torch.float64):
     """Autograd gradients of the train-step loss (network.py:213-222) in float64,
     with every ReLU's 0/1 derivative mask SUPPLIED by the caller (e.g. the GPU's
     own forward) instead of recomputed.  A pre-activation within fp32 rounding of
@@ -195,18 +252,22 @@ def masked_grads_fp64(state: dict, blocks: int, channels: int, x, pi, z, masks: 
     jumps there; fixing the masks makes the comparison well-conditioned.
     masks: a0 [B,C,15,15], h{i}, xo{i} (NCHW), fp [B,450], fv [B,225], hv [B,64];
     1.0 where the GPU's ReLU output was > 0.  Returns (grads dict, (pl, vl)), and
-    the fp64 pre-activations (numpy) as a third element when return_pre."""
-    net = RefNet(blocks, channels).double()
-    load_numpy_state(net, {k: (np.asarray(v, dtype=np.float64) if np.asarray(v).dtype.kind == "f" else v)
-                           for k, v in state.items()})
+    the fp64 pre-activations (numpy) as a third element when return_pre; with
+    return_buffers the net's BN buffers after the forward (bn_buffers) come last.
+    dtype: the arithmetic of the whole run (see masked_forward_fp64)."""
+    net = RefNet(blocks, channels).to(dtype)
+    load_numpy_state(net, state)
     net.train()
-    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
-    logits, value, pre = masked_forward_fp64(net, x, masks)
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype)
+    logits, value, pre = masked_forward_fp64(net, x, masks, dtype=dtype)
     pl = F.kl_div(F.log_softmax(logits, dim=1), t(pi), reduction="batchmean")
     vl = F.mse_loss(value, t(z))
     (pl + vl).backward()
     grads = {n: q.grad.numpy() for n, q in net.named_parameters()}
     losses = (float(pl.detach()), float(vl.detach()))
+    out = (grads, losses)
     if return_pre:
-        return grads, losses, {k: v.detach().numpy() for k, v in pre.items()}
-    return grads, losses
+        out += ({k: v.detach().numpy() for k, v in pre.items()},)
+    if return_buffers:
+        out += (bn_buffers(net),)
+    return out
