@@ -12,9 +12,13 @@
                        is a design aid (what a pack-time rule does to the operands' bits),
                        not a reference for GPU assertions: it has neither the fp32
                        accumulation order nor the MFMA's treatment of fp16 subnormals.
+* ``sharpen_policy``, ``sharp_net``, ``sharp_case`` -- nets with peaked policy outputs
+                       (policy_fc scaled by 2^k) and their CPU references: on a near-uniform
+                       softmax an absolute bar on probabilities is a weak bar on the logits.
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -193,6 +197,59 @@ def low_range_net(blocks: int, ch: int, which: str, k: int, calibrate: bool = Tr
     if calibrate:
         calib_bn(ref, seed=blocks * 1000 + ch)
     return ref
+
+
+# The peaked-policy nets of tests/test_gpu_sharp_outputs.py: policy_fc scaled by 2^k; k = 0
+# is the control.  At k = 4 rows saturate (top-2 gaps of 1e-8) and the softmax flattens again.
+SHARP = (2, 3)
+
+
+def sharpen_policy(net, k: int) -> None:
+    """policy_fc.weight, policy_fc.bias *= 2^k: every logit scales by exactly 2^k (a power
+    of two commutes with each rounding of the FC's products and sums), nothing else moves."""
+    f = 2.0 ** int(k)
+    with torch.no_grad():
+        net.policy_fc.weight.mul_(f)
+        net.policy_fc.bias.mul_(f)
+
+
+def sharp_net(blocks: int, ch: int, k: int):
+    """low_range_net's seeded, calibrated RefModel (its k = 0 control), policy sharpened by
+    2^k.  Every k of one shape shares everything but policy_fc with the others."""
+    ref = low_range_net(blocks, ch, "stem", 0)
+    sharpen_policy(ref.net, k)
+    return ref
+
+
+# (boards, synth_positions seed) per shape; the GPU forms take prefixes of these sets.  The
+# seeds are chosen so that the reference alone meets tests/test_oracle_sharp_outputs.py.
+SHARP_BOARDS = {(2, 128): (258, 2 + 128), (1, 256): (20, 1 + 256), (2, 64): (37, 2 + 64)}
+SHARP_PREFIXES = {(2, 128): (3, 37, 258), (1, 256): (20,), (2, 64): (37,)}
+ARGMAX_GAP = 2e-5     # rows whose fp64 masked top-2 gap is below this are exempt from the argmax check
+
+
+@functools.lru_cache(maxsize=None)
+def sharp_case(blocks: int, ch: int, k: int) -> dict:
+    """The sharpened net's state and its CPU references on the shape's board set, computed
+    once and read only: x, boards, players, fp32 and fp64 probs / values / logits (p32, v32,
+    l32, p64, v64, l64) and `exempt`, the rows whose fp64 masked top-2 gap is below ARGMAX_GAP."""
+    from oracle.boards import valid_mask
+    from oracle.ref_net import state_to_numpy
+    torch.set_num_threads(8)
+    n, seed = SHARP_BOARDS[(blocks, ch)]
+    boards, players = synth_positions(n, seed=seed)
+    x = encode_batch(boards, players)
+    ref = sharp_net(blocks, ch, k)
+    p32, v32, l32 = ref.predict(x, with_logits=True)
+    p64, v64, l64 = as_fp64(ref).predict(x, with_logits=True)
+    masks = np.stack([valid_mask(b) for b in boards])
+    srt = np.sort(p64 * masks, axis=1)
+    out = dict(state=state_to_numpy(ref.net), x=x, boards=np.asarray(boards), players=np.asarray(players), masks=masks,
+               p32=p32, v32=v32, l32=l32, p64=p64, v64=v64, l64=l64, exempt=(srt[:, -1] - srt[:, -2]) < ARGMAX_GAP)
+    for v in out.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return out
 
 
 def as_fp64(ref):

@@ -37,6 +37,20 @@ def argmax_check(probs, ref_probs, boards):
     assert not bad.any(), np.nonzero(bad)
 
 
+LOGIT_TOL = 2e-5
+
+
+def logits_check(m, x, l32, l64, tag):
+    """max|logit_gpu - logit_fp64| <= max(2e-5, 2 max|logit_cpu32 - logit_fp64|) on the planes
+    path under the current tuning keys.  |dp| <= 2 p (1 - p) max|dl| <= 0.5 max|dl|: 2e-5 is
+    the logit error that keeps every probability within 1e-5 however peaked the policy is
+    (on these near-uniform nets the 1e-5 bar on probabilities alone lets 1e-3 pass)."""
+    _, _, lg = m.engine.forward(torch.from_numpy(x), want_logits=True)
+    e, e_cpu = np.abs(lg.cpu().numpy() - l64).max(), np.abs(l32 - l64).max()
+    print(f"{tag} logits: |gpu-fp64|={e:.2e} |cpu32-fp64|={e_cpu:.2e}")
+    assert e <= max(LOGIT_TOL, 2 * e_cpu), (tag, e, e_cpu)
+
+
 @pytest.mark.parametrize("tag,blocks,ch", [("3x64", 3, 64), ("6x128", 6, 128)])
 def test_forward_matches_reference_goldens(tag, blocks, ch):
     g = load_golden(tag)
@@ -67,7 +81,7 @@ def test_forward_matches_oracle(blocks, ch, B):
     b, p = synth_positions(B, seed=B + ch)
     x = encode_batch(b, p)
     probs, values = m.predict(x)
-    rp, rv = ref.predict(x)
+    rp, rv, rl = ref.predict(x, with_logits=True)
     # fp64 re-run of the oracle.  Untrained (seeded-init) weights are ill-conditioned
     # enough that fp32 itself drifts ~1e-5 from the exact result (10x256: the fp32
     # oracle is 1.2e-5 off fp64, measured), so the gate is: deviation from the exact
@@ -75,13 +89,14 @@ def test_forward_matches_oracle(blocks, ch, B):
     r64 = RefModel(blocks, ch, dtype=torch.float64)
     r64.net.load_state_dict({k: (v.double() if v.dtype.is_floating_point else v)
                              for k, v in ref.net.state_dict().items()})
-    p64, v64 = r64.predict(x)
+    p64, v64, l64 = r64.predict(x, with_logits=True)
     for name, got, r32, r_64 in (("probs", probs, rp, p64), ("values", values, rv, v64)):
         e_gpu = np.abs(got - r_64).max()
         e_cpu = np.abs(r32 - r_64).max()
         print(f"{blocks}x{ch} {name}: |gpu-fp64|={e_gpu:.2e} |cpu32-fp64|={e_cpu:.2e} "
               f"|gpu-cpu32|={np.abs(got - r32).max():.2e}")
         assert e_gpu <= max(TOL, 2 * e_cpu), (name, e_gpu, e_cpu)
+    logits_check(m, x, rl, l64, f"{blocks}x{ch}")
     argmax_check(probs, rp, b)
 
 
@@ -551,7 +566,14 @@ def test_h3_matches_fp32_forward_and_oracle(blocks, ch, B, cls):
     r64 = RefModel(blocks, ch, dtype=torch.float64)
     r64.net.load_state_dict({k: (v.double() if v.dtype.is_floating_point else v)
                              for k, v in ref.net.state_dict().items()})
-    pr, vr = r64.predict(x)
+    pr, vr, lr = r64.predict(x, with_logits=True)
+    l32 = ref.predict(x, with_logits=True)[2]
+    for arith in (0, cls):
+        prev = lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, arith)
+        try:
+            logits_check(m, x, l32, lr, f"{blocks}x{ch} key19={arith}")
+        finally:
+            lib.azg_pv_set_tuning(TUNE.EVAL_ARITH, prev)
     for name, a32, a16, a64 in (("probs", p32, p16, pr), ("values", v32, v16, vr)):
         e32, e16 = np.abs(a32 - a64).max(), np.abs(a16 - a64).max()
         print(f"{blocks}x{ch} key19={cls} {name}: |fp32-fp64|={e32:.2e} |h3-fp64|={e16:.2e} "

@@ -131,6 +131,14 @@ def test_score_batch_matches_the_oracle(blocks, ch):
     boards, players = synth_positions(B, seed=B + ch)
     x = encode_batch(boards, players)
     pi, z = synth_targets(B, seed=B + ch + 1)
+    score_against_oracle(ref, x, pi, z, f"{blocks}x{ch}")
+
+
+def score_against_oracle(ref, x, pi, z, tag):
+    """score_batch of a model with ref's weights against the fp64 restatement on the fp64
+    oracle's outputs; the gate per continuous key is this file's item 3.  Returns (gpu
+    summary, fp64 summary, fp64 logits) for further checks."""
+    blocks, ch, B = len(ref.net.res_blocks), ref.net.channels, len(x)
     _, v64, l64 = as_fp64(ref).predict(x, with_logits=True)
     ref64 = summary_from_records(score_records(l64, v64, pi, z))
     # the fp32 CPU oracle through torch's own functions
@@ -149,11 +157,12 @@ def test_score_batch_matches_the_oracle(blocks, ch):
     failures = []
     for k in CONTINUOUS_KEYS:
         d_gpu, d_cpu = abs(gpu[k] - ref64[k]), abs(cpu32[k] - ref64[k])
-        print(f"{blocks}x{ch} {k}: ref64={ref64[k]:.9g} |gpu-ref64|={d_gpu:.2e} |cpu32-ref64|={d_cpu:.2e} "
+        print(f"{tag} {k}: ref64={ref64[k]:.9g} |gpu-ref64|={d_gpu:.2e} |cpu32-ref64|={d_cpu:.2e} "
               f"|gpu-cpu32|={abs(gpu[k] - cpu32[k]):.2e}")
         if not d_gpu <= max(1e-5 * abs(ref64[k]) + 1e-7, 2 * d_cpu):
             failures.append((k, d_gpu, d_cpu))
     assert not failures, failures
+    return gpu, ref64, l64
 
 
 # ---------------------------------------------------------------- 4. host, device, chunked
