@@ -55,6 +55,8 @@ _SIGS = {
     "azg_pv_mark_dirty": (ctypes.c_int32, [_P]),
     "azg_pv_bind_counters": (ctypes.c_int32, [_P, _P]),
     "azg_pv_num_bn_layers": (ctypes.c_int32, [_P]),
+    "azg_pv_bind_ema": (ctypes.c_int32, [_P, _P, _P, ctypes.c_float]),
+    "azg_pv_get_ema": (ctypes.c_int32, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_float)]),
     "azg_pv_forward": (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P, _P, _P, _P]),
     "azg_pv_forward_boards": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, _P, _P, _P, _P]),
     "azg_pv_forward_boards_sym": (ctypes.c_int32, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P]),

@@ -5,6 +5,7 @@
 // also works without a GPU: device work is only reached after azg_pv_bind).
 #include "../../../include/azg_pv.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -97,6 +98,29 @@ int main()
             CHECK(azg_pv_set_eval_precision(h, AZG_PV_EVAL_EXACT) == 0);
             CHECK(azg_pv_get_eval_precision(h) == AZG_PV_EVAL_EXACT);
         }
+        {   // azg_pv_bind_ema / azg_pv_get_ema: host state only, checked before any device call
+            float ep = 0.f, eb = 0.f, *gp = &dummy, *gb = &dummy, gd = -1.f;
+            const auto names_it = [] { return std::strstr(azg_pv_last_error(), "azg_pv_bind_ema") != nullptr; };
+            const auto bound = [&](float* p, float* b, float d) {
+                return azg_pv_get_ema(h, &gp, &gb, &gd) == (p ? 1 : 0) && gp == p && gb == b && gd == d;
+            };
+            CHECK(bound(nullptr, nullptr, 0.f));   // off by default
+            CHECK(azg_pv_bind_ema(h, &ep, nullptr, 0.9f) != 0 && names_it());
+            CHECK(azg_pv_bind_ema(h, nullptr, &eb, 0.9f) != 0 && names_it());
+            CHECK(azg_pv_bind_ema(h, &ep, &eb, 1.f) != 0 && names_it());
+            CHECK(std::strstr(azg_pv_last_error(), "decay") != nullptr);
+            CHECK(azg_pv_bind_ema(h, &ep, &eb, -0.1f) != 0 && names_it());
+            CHECK(azg_pv_bind_ema(h, &ep, &eb, std::nanf("")) != 0 && names_it());
+            CHECK(bound(nullptr, nullptr, 0.f));   // refused calls change nothing
+            CHECK(azg_pv_bind_ema(h, &ep, &eb, 0.999f) == 0 && bound(&ep, &eb, 0.999f));
+            CHECK(azg_pv_bind_ema(h, &ep, nullptr, 0.5f) != 0 && azg_pv_bind_ema(h, &eb, &ep, 2.f) != 0);
+            CHECK(bound(&ep, &eb, 0.999f));
+            CHECK(azg_pv_bind_ema(h, nullptr, nullptr, std::nanf("")) == 0);   // unbind ignores decay
+            CHECK(bound(nullptr, nullptr, 0.f));
+            CHECK(azg_pv_bind_ema(h, &eb, &ep, 0.f) == 0 && bound(&eb, &ep, 0.f));   // bind -> unbind -> bind
+            CHECK(azg_pv_get_ema(h, nullptr, nullptr, nullptr) == 1);
+            CHECK(azg_pv_bind_ema(h, nullptr, nullptr, 0.f) == 0 && azg_pv_get_ema(h, nullptr, nullptr, nullptr) == 0);
+        }
         CHECK(azg_pv_train_backward(h, &dummy, &dummy, &dummy, 4, &dummy, nullptr) != 0);
         CHECK(azg_pv_train_apply(h, &dummy, &dummy, 1, 1e-3f, 0.9f, 0.999f, 1e-8f, 1e-4f, 3.f, nullptr, nullptr) != 0);
         CHECK(azg_pv_destroy(h) == 0);
@@ -119,6 +143,9 @@ int main()
     CHECK(azg_pv_last_seq(nullptr) == 0);
     CHECK(azg_pv_set_eval_precision(nullptr, AZG_PV_EVAL_EXACT) != 0);
     CHECK(azg_pv_get_eval_precision(nullptr) == -1);
+    CHECK(azg_pv_bind_ema(nullptr, nullptr, nullptr, 0.9f) != 0);
+    CHECK(std::strstr(azg_pv_last_error(), "azg_pv_bind_ema: null handle") != nullptr);
+    CHECK(azg_pv_get_ema(nullptr, nullptr, nullptr, nullptr) == -1);
     CHECK(azg_pv_tower_diag_clear(nullptr, nullptr) != 0);
     CHECK(azg_pv_bind(nullptr, nullptr, nullptr, nullptr) != 0);
     // replay gather: every argument is checked before any device call

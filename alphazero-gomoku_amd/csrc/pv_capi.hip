@@ -174,6 +174,33 @@ int32_t azg_pv_bind_counters(azg_pv* h, int64_t* num_batches_tracked)
     return 0;
 }
 
+int32_t azg_pv_bind_ema(azg_pv* h, float* ema_params, float* ema_bn, float decay)
+{
+    // host state only: no device call, before or after azg_pv_bind
+    if (!h) return fail("azg_pv_bind_ema: null handle");
+    if (!ema_params != !ema_bn)
+        return fail("azg_pv_bind_ema: ema_params and ema_bn must both be set (bind) or both be null (unbind)");
+    if (!ema_params) {   // unbind: decay is ignored
+        h->ema_params = h->ema_bn = nullptr;
+        h->ema_decay = 0.f;
+        return 0;
+    }
+    if (!(decay >= 0.f && decay < 1.f)) return fail("azg_pv_bind_ema: decay must be in [0, 1)");   // NaN fails too
+    h->ema_params = ema_params;
+    h->ema_bn = ema_bn;
+    h->ema_decay = decay;
+    return 0;
+}
+
+int32_t azg_pv_get_ema(const azg_pv* h, float** ema_params, float** ema_bn, float* decay)
+{
+    if (!h) return -1;
+    if (ema_params) *ema_params = h->ema_params;
+    if (ema_bn) *ema_bn = h->ema_bn;
+    if (decay) *decay = h->ema_decay;
+    return h->ema_params ? 1 : 0;
+}
+
 int32_t azg_pv_num_bn_layers(const azg_pv* h) { return h ? (int32_t)h->bn_desc.size() : -1; }
 
 int32_t azg_pv_mark_dirty(azg_pv* h)

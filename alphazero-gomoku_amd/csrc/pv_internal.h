@@ -215,6 +215,11 @@ struct azg_pv {
     float* grads = nullptr;
     float* bn = nullptr;
     int64_t* nbt = nullptr;   // optional: num_batches_tracked per BN layer (azg_pv_bind_counters)
+    // optional: the running average of the weights (azg_pv_bind_ema; both null: off), moved by
+    // every train step the Adam kernel commits
+    float* ema_params = nullptr;   // [nparams]
+    float* ema_bn = nullptr;       // [nbn]
+    float ema_decay = 0.f;
     bool dirty = true;
     bool train_packs = false;   // wpack / wdpack / wstem / wfc hold the current parameters (train_apply, key 36)
     bool bn_bak_ok = false;     // the train workspace's BN backup holds the running stats the next step starts from

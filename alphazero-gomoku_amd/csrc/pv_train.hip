@@ -594,12 +594,20 @@ struct BnKeep {
     int nlayers;
     unsigned* skips;      // host-mapped count of skipped steps (azg_pv_train_status)
 };
+// The running average of the weights (azg_pv_bind_ema; all null: off).  A committed step
+// moves it towards the step's new parameters and running stats, e += w (x - e) with
+// w = 1 - decay; a skipped step returns before any access to it.
+struct Ema {
+    float* p;             // [n] average of the parameters
+    float* bn;            // [nbn] average of the BN running stats
+    float w;
+};
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                    const double* __restrict__ part, int nb, float max_norm,
                                                    float* __restrict__ scal, float* __restrict__ total_norm,
                                                    float lr_bc1, float b1w, float b2, float one_m_b2, float bc2_sqrt,
-                                                   float eps, float wd, BnKeep k)
+                                                   float eps, float wd, BnKeep k, Ema ema)
 {
     const int64_t gtid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, gstride = (int64_t)gridDim.x * blockDim.x;
     if (g[n] != 0.f) {   // skip: undo the step's running-stat updates
@@ -609,7 +617,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         if (gtid == 0 && k.skips) __hip_atomic_fetch_add(k.skips, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
-    for (int64_t i = gtid; i < k.nbn; i += gstride) k.bn_bak[i] = k.bn[i];
+    for (int64_t i = gtid; i < k.nbn; i += gstride) {
+        const float s = k.bn[i];   // the running stat this step's train_backward produced
+        k.bn_bak[i] = s;
+        if (ema.bn) {
+            const float e = ema.bn[i];
+            ema.bn[i] = fmaf(ema.w, s - e, e);
+        }
+    }
     if (k.nbt)
         for (int64_t i = gtid; i < k.nlayers; i += gstride) k.nbt_bak[i] = k.nbt[i];
     __shared__ double red[8];
@@ -625,6 +640,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         if (total_norm) total_norm[0] = tn;
     }
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        // The roundings of this body are pinned: left to -ffp-contract=fast, which products fuse
+        // with their sums depends on what else the loop holds (the compiler packs the
+        // multiplies two wide and then leaves the sums unfused; with the average's two extra
+        // instructions in the loop it fused them instead, and the two-step goldens moved).
+        // Every product and sum below rounds on its own, except the parameter update, which
+        // is one fma -- the instruction sequence the kernel compiled to before it kept an average.
+#pragma clang fp contract(off)
         float gi = g[i] * coef;
         g[i] = gi;
         const float pi = p[i];
@@ -634,9 +656,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
         float vi = v[i] * b2;
         vi = vi + one_m_b2 * gi * gi;              // addcmul
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi + (-lr_bc1) * (mi / denom);      // addcdiv
+        const float pnew = fmaf(-lr_bc1, mi / denom, pi);   // addcdiv: pi + (-lr_bc1) * (mi / denom), fused
+        p[i] = pnew;
         m[i] = mi;
         v[i] = vi;
+        if (ema.p) {
+            const float e = ema.p[i];
+            ema.p[i] = fmaf(ema.w, pnew - e, e);
+        }
     }
 }
 
@@ -1190,9 +1217,10 @@ int32_t train_apply(azg_pv* h, float* exp_avg, float* exp_avg_sq, int64_t step, 
     // 1024 workgroups, grid-stride: each reduces the 1024 norm partials (8 KB) itself
     const BnKeep keep{h->bn, w->bn_bak, (int)h->nbn, h->nbt, w->nbt_bak, (int)h->bn_desc.size(),
                       h->train_ovf_dev ? h->train_ovf_dev + kTrainSkips : nullptr};
+    const Ema ema{h->ema_params, h->ema_bn, (float)(1.0 - (double)h->ema_decay)};
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n) < 1024 ? grid_for(n) : 1024), dim3(256), 0, st, h->params,
                        h->grads, exp_avg, exp_avg_sq, n, w->npart, nb, max_norm, w->scal, total_norm, lr_bc1,
-                       (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2), bc2_sqrt, eps, wd, keep);
+                       (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2), bc2_sqrt, eps, wd, keep, ema);
     AZG_CK(hipGetLastError(), "apply: adam");
     // every pack of the next step (and the eval BN fold) from the new parameters, on
     // this stream right behind Adam: the next train step starts without a repack

@@ -104,13 +104,16 @@ def grad_hook():
 
 
 def broadcast_model(model, src: int = 0) -> None:
-    """Make every replica identical to `src`: params, BN stats and counters, Adam
-    moments and the Adam step counter (bias correction)."""
+    """Make every replica identical to `src`: params, BN stats and counters, the weight
+    average if the model keeps one, Adam moments and the Adam step counter (bias correction)."""
     if world() == 1:
         return
     eng = model.engine
     for t in (eng.flat_params, eng.flat_bn, eng.flat_nbt):
         broadcast_(t, src)
+    if eng.flat_ema is not None:   # the weight average (every rank has EMA on, or none)
+        broadcast_(eng.flat_ema, src)
+        broadcast_(eng.flat_ema_bn, src)
     opt = model.optimizer
     broadcast_(opt.flat_exp_avg, src)
     broadcast_(opt.flat_exp_avg_sq, src)
@@ -124,9 +127,14 @@ def broadcast_model(model, src: int = 0) -> None:
 
 
 def sync_bn_stats(model) -> None:
-    """Average BN running statistics (each rank saw its own local batches)."""
+    """Average BN running statistics (each rank saw its own local batches), and their
+    running average when the model keeps one: the averaged PARAMETERS need no communication
+    (the parameters are bitwise equal on every rank after every step), the averaged
+    statistics do."""
     if world() > 1:
         allreduce_mean_(model.engine.flat_bn)
+        if model.engine.flat_ema_bn is not None:
+            allreduce_mean_(model.engine.flat_ema_bn)
         model.engine.mark_dirty()
 
 

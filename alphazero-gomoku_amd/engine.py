@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -119,6 +120,56 @@ class PolicyValueEngine:
         self.recoveries = 0         # tower launches recomputed per layer (recover)
         self.train_recoveries = 0   # train steps skipped on the device and redone in fp32 (network.train_batch)
         self._unsettled = []        # launch numbers of forwards no host sync has settled yet (predict_device)
+        # the running average of the weights (enable_ema): off, and nothing allocated, by default
+        self.flat_ema = None        # [nparam], laid out like flat_params
+        self.flat_ema_bn = None     # [nbn], laid out like flat_bn
+        self.ema_decay = None
+
+    # -- weight average (EMA) -----------------------------------------------
+    def enable_ema(self, decay: float) -> None:
+        """Keep e += (1 - decay) (x - e) of the parameters and the BN running stats, moved
+        inside the Adam kernel by every train step that commits (include/azg_pv.h
+        azg_pv_bind_ema; a step the device skips leaves it alone).  The average starts at
+        the current weights, copied on the current stream.  Calling it again changes the
+        decay and restarts the average."""
+        d = float(decay)
+        if not 0.0 <= d < 1.0:   # NaN fails too
+            raise ValueError(f"ema_decay must be in [0, 1), got {decay!r}")
+        with torch.no_grad():
+            ema, ema_bn = self.flat_params.clone(), self.flat_bn.clone()
+        check(self.lib.azg_pv_bind_ema(self.h, ptr(ema), ptr(ema_bn), d), self.lib)
+        self.flat_ema, self.flat_ema_bn, self.ema_decay = ema, ema_bn, d
+
+    def disable_ema(self) -> None:
+        if self.flat_ema is not None:
+            check(self.lib.azg_pv_bind_ema(self.h, None, None, 0.0), self.lib)
+            self.flat_ema = self.flat_ema_bn = self.ema_decay = None
+
+    def reset_ema(self) -> None:
+        """The average back at the current weights (after loading weights through torch)."""
+        if self.flat_ema is None:
+            raise RuntimeError("reset_ema: EMA is off (enable_ema)")
+        with torch.no_grad():
+            self.flat_ema.copy_(self.flat_params)
+            self.flat_ema_bn.copy_(self.flat_bn)
+
+    def ema_weight(self) -> float:
+        """The fp32 weight 1 - decay the kernel applies, as the library computes it."""
+        return float(np.float32(1.0 - float(np.float32(self.ema_decay))))
+
+    def ema_source(self, t: torch.Tensor):
+        """For a tensor of net.state_dict() (a view of one of the flat buffers): the same
+        elements of the average -- of flat_ema for a parameter, of flat_ema_bn for a running
+        mean or variance -- or the tensor itself for a counter."""
+        o, k = int(t.storage_offset()), t.numel()
+        base = t.untyped_storage().data_ptr()
+        if base == self.flat_params.untyped_storage().data_ptr():
+            return self.flat_ema[o:o + k].view(t.shape)
+        if base == self.flat_bn.untyped_storage().data_ptr():
+            return self.flat_ema_bn[o:o + k].view(t.shape)
+        if base == self.flat_nbt.untyped_storage().data_ptr():
+            return t
+        raise RuntimeError("a tensor of the module's state no longer lives in the engine's flat buffers")
 
     # -- housekeeping -------------------------------------------------------
     def _versions(self):

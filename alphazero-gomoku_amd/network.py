@@ -12,7 +12,9 @@ Same public surface as the reference (network.py:9-265):
     ``train_step`` aliases named by the north star, and device-resident variants
     (``predict_device``) for the batched self-play driver, and ``score_batch`` /
     ``score_batch_device``: the train step's two losses and policy / value metrics of a
-    batch from the eval forward, changing nothing.
+    batch from the eval forward, changing nothing; and, opt-in (``ema_decay``), an
+    exponential moving average of the weights kept inside the train step's Adam kernel
+    (``enable_ema``, ``ema_state_dict``, ``ema_model``).
 
 Differences, by design: the device must be a HIP GPU (there is no CPU path: the
 reference's CPU fallback, network.py:152, raises here) and the board must be 15x15.
@@ -353,13 +355,17 @@ class PyTorchModel:
                  channels: int = 64,
                  lr: float = 1e-3,
                  weight_decay: float = 1e-4,
-                 eval_precision: str = "exact"):
+                 eval_precision: str = "exact",
+                 ema_decay: Optional[float] = None):
         # "exact": every eval forward holds 1e-5 fp32 parity; "fp16": one-product fp16
         # residual convs (self-play leaf evaluation; 128-channel nets).  Checked before any
         # device work; never written to checkpoints (save / load keep the reference's format)
         if eval_precision not in PolicyValueEngine.EVAL_PRECISIONS:
             raise ValueError(f"eval_precision must be one of {PolicyValueEngine.EVAL_PRECISIONS}, "
                              f"got {eval_precision!r}")
+        # ema_decay (None: off, nothing allocated): enable_ema(ema_decay) once the net is built
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be None or in [0, 1), got {ema_decay!r}")
         self.board_size = board_size
         self.action_size = action_size if action_size is not None else board_size * board_size
         self.device = device or ("cuda" if torch.cuda.is_available() else "cpu")
@@ -376,12 +382,78 @@ class PyTorchModel:
         self.grad_hook = None                           # DP: all-reduce of the flat grads (+ skip word)
         self._losses = None
         self._skips_seen = 0                            # device-skipped steps already accounted for
+        self._ctor = dict(board_size=board_size, action_size=self.action_size, device=self.device,
+                          n_res_blocks=n_res_blocks, channels=channels)   # ema_model builds its twin from it
+        self._ema_twin = None
         if eval_precision != "exact":
             self.set_eval_precision(eval_precision)
+        if ema_decay is not None:
+            self.enable_ema(ema_decay)
 
     @property
     def engine(self) -> PolicyValueEngine:
         return self.net.engine
+
+    # ---------------- weight average (EMA) ----------------
+    @property
+    def ema_decay(self) -> Optional[float]:
+        return self.engine.ema_decay
+
+    def enable_ema(self, decay: float) -> None:
+        """Keep an exponential moving average of the weights while the raw weights train:
+        after every train step that commits, e += (1 - decay) (x - e) for every parameter
+        and every BN running mean and variance, inside the step's Adam kernel (no second
+        pass, and a step the device skips does not move it).  The average starts at the
+        current weights.  Read it with ema_state_dict() or ema_model()."""
+        self.engine.enable_ema(decay)
+
+    def disable_ema(self) -> None:
+        """Stop averaging and free the average (and ema_model's twin)."""
+        self.engine.disable_ema()
+        self._ema_twin = None
+
+    def reset_ema(self) -> None:
+        """Set the average back to the current weights: call it after loading weights
+        through torch (net.load_state_dict), which the average does not see."""
+        self.engine.reset_ema()
+
+    def ema_state_dict(self) -> dict:
+        """The average as clones shaped and keyed exactly like net.state_dict(): parameters
+        and BN running means / variances from the average, num_batches_tracked from the
+        live counters.  RuntimeError when EMA is off."""
+        eng = self.engine
+        if eng.flat_ema is None:
+            raise RuntimeError("ema_state_dict: EMA is off (PyTorchModel(ema_decay=...) or enable_ema)")
+        return {k: eng.ema_source(v).detach().clone() for k, v in self.net.state_dict().items()}
+
+    def _load_ema_state(self, sd: dict) -> None:
+        eng = self.engine
+        with torch.no_grad():
+            for k, v in self.net.state_dict().items():
+                dst = eng.ema_source(v)
+                if dst is not v:   # the counters are the live ones
+                    dst.copy_(sd[k])
+
+    def ema_model(self) -> "PyTorchModel":
+        """A second PyTorchModel of the same shape on the same device that holds the
+        average: created on the first call, and on every call refreshed from the average
+        by device-to-device copies on the current stream (counters: the live ones).  It has
+        its own eval precision ("exact" unless set on it), its own board evaluators and no
+        EMA of its own; hand it to self-play or gating like any model."""
+        eng = self.engine
+        if eng.flat_ema is None:
+            raise RuntimeError("ema_model: EMA is off (PyTorchModel(ema_decay=...) or enable_ema)")
+        if self._ema_twin is None:
+            with torch.random.fork_rng(devices=[]):   # the twin's weight init draws nothing from the caller's RNG
+                self._ema_twin = PyTorchModel(**self._ctor)
+            self._ema_twin.net.train(self.net.training)
+        t = self._ema_twin.engine
+        with torch.no_grad():
+            t.flat_params.copy_(eng.flat_ema)
+            t.flat_bn.copy_(eng.flat_ema_bn)
+            t.flat_nbt.copy_(eng.flat_nbt)
+        t.mark_dirty()
+        return self._ema_twin
 
     @property
     def eval_precision(self) -> str:
@@ -635,7 +707,9 @@ class PyTorchModel:
 
     # ---------------- checkpoints ----------------
     def save(self, path: str) -> None:
-        """network.py:240-248 format: {"net", "opt", "board_size", "action_size"}."""
+        """network.py:240-248 format: {"net", "opt", "board_size", "action_size"}; with EMA
+        on, one more key, "ema": {"decay", "net": ema_state_dict()} (the reference's loader
+        reads "net" and "opt" only)."""
         d = os.path.dirname(path)
         if d:
             os.makedirs(d, exist_ok=True)
@@ -646,14 +720,24 @@ class PyTorchModel:
         opt_sd = {"state": {i: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
                             for i, st in opt_sd["state"].items()},
                   "param_groups": opt_sd["param_groups"]}
-        torch.save({"net": net_sd, "opt": opt_sd, "board_size": self.board_size,
-                    "action_size": self.action_size}, path)
+        state = {"net": net_sd, "opt": opt_sd, "board_size": self.board_size, "action_size": self.action_size}
+        if self.ema_decay is not None:
+            state["ema"] = {"decay": self.ema_decay, "net": self.ema_state_dict()}
+        torch.save(state, path)
 
     def load(self, path: str, map_location: Optional[str] = None) -> None:
-        """network.py:250-258; optimizer-state errors are ignored as in the reference."""
+        """network.py:250-258; optimizer-state errors are ignored as in the reference.
+        With EMA on, the average is restored from the file's "ema" key (this model keeps its
+        own decay), or reset to the loaded weights when the file has none; with EMA off the
+        key is ignored."""
         map_location = map_location or self.device
         state = torch.load(path, map_location=map_location, weights_only=True)
         self.net.load_state_dict(state["net"])
+        if self.ema_decay is not None:
+            if state.get("ema") is not None:
+                self._load_ema_state(state["ema"]["net"])
+            else:
+                self.reset_ema()
         if "opt" in state and state["opt"] is not None:
             try:
                 self.optimizer.load_state_dict(state["opt"])

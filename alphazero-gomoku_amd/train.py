@@ -195,7 +195,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     channels: int = 64, device: Optional[str] = None, max_moves: Optional[int] = None,
                     device_buffer: bool = False, leaf_symmetry=None, eval_symmetry=None,
                     selfplay_precision: Optional[str] = None, score_new_games: bool = False,
-                    score_max_examples: int = 4096, history: Optional[list] = None, **reference_worker_kwargs):
+                    score_max_examples: int = 4096, history: Optional[list] = None,
+                    ema_decay: Optional[float] = None, **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -224,7 +225,16 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     "last_train_loss"} (the score dicts are None without score_new_games or without local
     examples; last_train_loss is None when the iteration did not train).  Scoring consumes
     no RNG and changes nothing about the buffer, the steps or gating; with the defaults no
-    scoring call is made."""
+    scoring call is made.
+
+    ema_decay (None or in [0, 1)): every candidate keeps an exponential moving average of
+    its weights (PyTorchModel.enable_ema), started at the weights the iteration starts from
+    and moved by every train step inside the Adam kernel.  Gating plays the AVERAGE
+    (model_candidate.ema_model()) against model_best, and on acceptance model_best takes the
+    averaged weights with the candidate's optimiser state; the raw weights only train.
+    history entries carry "ema_decay".  None, the default, makes no EMA call."""
+    if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay must be None or in [0, 1), got {ema_decay!r}")
     if selfplay_precision not in (None, "exact", "fp16"):
         raise ValueError(f"selfplay_precision must be None, 'exact' or 'fp16', got {selfplay_precision!r}")
     r, w, _, dev = D.init_from_env()
@@ -243,6 +253,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         model_best = _new_model(board_size, action_size, device, n_res_blocks, channels)
     D.broadcast_model(model_best)
     model_candidate = _new_model(board_size, action_size, device, n_res_blocks, channels, like=model_best)
+    if ema_decay is not None:
+        model_candidate.enable_ema(ema_decay)
 
     suffix = "" if r == 0 else f"_rank{r}"
     buffer_path = os.path.join(model_dir, f"replay_buffer_latest{suffix}.pkl")
@@ -311,12 +323,14 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                 print(_score_line("after training", score_after))
         if history is not None:
             history.append({"iteration": it, "new_games_before": score_before, "new_games_after": score_after,
-                            "last_train_loss": loss_info})
+                            "last_train_loss": loss_info, "ema_decay": ema_decay})
 
         te = time.time()
+        # with EMA on, the gated net is the average of the candidate's weights, not its last step
+        gated = model_candidate if ema_decay is None else model_candidate.ema_model()
         try:
-            ev_new, ev_best = ((model_candidate, model_best) if eval_symmetry is None else
-                               (model_candidate.symmetric(eval_symmetry), model_best.symmetric(eval_symmetry)))
+            ev_new, ev_best = ((gated, model_best) if eval_symmetry is None else
+                               (gated.symmetric(eval_symmetry), model_best.symmetric(eval_symmetry)))
             new_wins, win_rate, draws = evaluate_models(ev_new, ev_best, game_name, n_games=eval_games,
                                                         n_simulations=eval_mcts_simulations, cpuct=cpuct)
         except TowerFault:
@@ -332,12 +346,15 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         if win_rate >= win_rate_threshold:
             if main:
                 print(" candidate accepted -> best")
-            model_best.net.load_state_dict(model_candidate.net.state_dict())
+            model_best.net.load_state_dict(model_candidate.net.state_dict() if ema_decay is None
+                                           else model_candidate.ema_state_dict())
             model_best.optimizer.load_state_dict(model_candidate.optimizer.state_dict())
         elif main:
             print(" candidate rejected -> restore from best")
         model_candidate = _new_model(board_size, action_size, device, n_res_blocks, channels, like=model_best,
                                      with_opt=True)
+        if ema_decay is not None:
+            model_candidate.enable_ema(ema_decay)
         if main and it % save_every == 0:
             path = os.path.join(model_dir, f"snapshot_iter{it}_{datetime.now():%Y%m%d_%H%M%S}.pt")
             model_best.save(path)

@@ -84,6 +84,26 @@ int64_t azg_pv_grad_count(const azg_pv* h);
 int32_t azg_pv_bind_counters(azg_pv* h, int64_t* num_batches_tracked);
 int32_t azg_pv_num_bn_layers(const azg_pv* h);
 
+/* Optional: a running average of the weights (EMA), kept by the Adam kernel.  The caller
+ * owns two device buffers, ema_params of azg_pv_param_count floats and ema_bn of
+ * azg_pv_bn_count floats, and initialises them (usually to the current parameters and BN
+ * running stats).  While bound, every azg_pv_train_apply that COMMITS moves them inside its
+ * own pass over the parameters (no extra launch):
+ *   ema_params[i] = fmaf(w, p_new[i] - ema_params[i], ema_params[i])
+ *   ema_bn[i]     = fmaf(w, bn[i]    - ema_bn[i],     ema_bn[i])
+ * with w = (float)(1.0 - (double)decay), p_new the parameter the step just wrote and bn the
+ * running stats the step's azg_pv_train_backward produced.  A step that does not commit
+ * (the skip word, azg_pv_train_apply) does not touch them.  The average is never read by
+ * the library's forwards: copy it into a second handle's buffers to evaluate it.
+ * Both pointers NULL unbinds (decay is then ignored).  Returns nonzero (azg_pv_last_error
+ * names azg_pv_bind_ema) and leaves the handle as it was on a null handle, exactly one NULL
+ * pointer, or a decay outside [0, 1) or NaN.  Makes no device call; may be called before or
+ * after azg_pv_bind.
+ * azg_pv_get_ema: 1 if an average is bound, 0 if not, -1 on a null handle; the non-NULL
+ * outputs (HOST pointers) receive the bound pointers and decay (NULL, NULL, 0 when off). */
+int32_t azg_pv_bind_ema(azg_pv* h, float* ema_params, float* ema_bn, float decay);
+int32_t azg_pv_get_ema(const azg_pv* h, float** ema_params, float** ema_bn, float* decay);
+
 /* Parameters or BN stats changed outside the library (load_state_dict, copy_, a
  * write through the bound pointers, a collective that rewrites them): re-derive
  * packed weights / folded BN before the next forward AND the next train step.
@@ -170,7 +190,8 @@ int32_t azg_pv_train_backward(azg_pv* h, const float* x, const float* pis,
  * params, grads and moments are left as they are, the BN running stats and counters
  * are restored to what the step started from, and the skipped-step count
  * (azg_pv_train_status) advances.  The caller then redoes the step, e.g. after
- * azg_pv_train_fp32_once, with the same `step`. */
+ * azg_pv_train_fp32_once, with the same `step`.  A committed step also moves the weight
+ * average bound with azg_pv_bind_ema, if any; a skipped one leaves it as it is. */
 int32_t azg_pv_train_apply(azg_pv* h, float* exp_avg, float* exp_avg_sq,
                            int64_t step, float lr, float beta1, float beta2,
                            float eps, float weight_decay, float max_norm,
