@@ -1,5 +1,6 @@
 // Host AddressSanitizer driver of the policy/value C-ABI's host side
-// (include/azg_pv.h, csrc/pv_capi.hip built with -Xarch_host -fsanitize=address):
+// (include/azg_pv.h, csrc/pv_capi.hip and csrc/pv_eval.hip built with -Xarch_host
+// -fsanitize=address):
 // handle lifecycle, flat-buffer layout for every supported shape, the status and
 // tuning entry points, and every argument-error path.  No kernel runs (the driver
 // also works without a GPU: device work is only reached after azg_pv_bind).

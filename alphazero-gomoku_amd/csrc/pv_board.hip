@@ -293,7 +293,7 @@ __global__ __launch_bounds__(kBtThreads, 4) void board_tower(const BoardArgs a)
 #undef AZG_BT_EPI
             }
             if (bad && a.ring_ovf && a.seq)
-                __hip_atomic_store(a.ring_ovf + (a.seq & (kH3RingSize - 1)), a.seq, __ATOMIC_RELAXED,
+                __hip_atomic_store(a.ring_ovf + (a.seq & (kTowerRing - 1)), a.seq, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
             // the next conv reads what every wave wrote (and the next stage's chunk, issued at
             // the top of this conv's last stage, has landed: that stage's wait)

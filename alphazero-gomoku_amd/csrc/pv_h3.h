@@ -384,7 +384,7 @@ __device__ __forceinline__ void h3_tile(const float* __restrict__ in, const floa
             }
         }
         if (bad && guard.ring && guard.seq)
-            __hip_atomic_store(guard.ring + (guard.seq & (kH3RingSize - 1)), guard.seq, __ATOMIC_RELAXED,
+            __hip_atomic_store(guard.ring + (guard.seq & (kTowerRing - 1)), guard.seq, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }

@@ -9,6 +9,7 @@
 // K-chunk of 32 is one contiguous block.
 #pragma once
 #include "pv_common.h"
+#include "pv_posted.h"
 
 #ifndef AZG_EVAL_REMAT
 #define AZG_EVAL_REMAT 0   // study: 1 = per-tap addresses in the fp32 bodies too
@@ -260,7 +261,6 @@ __device__ __forceinline__ int h3_dgrad_exp(unsigned maxbits)
     const int k = m > 0.f && __builtin_isfinite(m) ? 14 - ilogbf(m) : 0;
     return k < -100 ? -100 : k > 100 ? 100 : k;   // 2^k and the epilogue's 2^-(e + k) stay normal
 }
-constexpr unsigned kH3RingSize = 256;   // = kTowerRing (pv_internal.h)
 
 // key of the 16-B slot swizzle of halo row `row` (padded-pixel index): the padded
 // board position v = yy*15 + xx (see halo_tile)
@@ -356,7 +356,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<
             const bool fin = __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]) &&
                              __builtin_isfinite(v[3]);
             if (!fin && m0 + row < M && guard->ring && guard->seq)
-                __hip_atomic_store(guard->ring + (guard->seq & (kH3RingSize - 1)), guard->seq, __ATOMIC_RELAXED,
+                __hip_atomic_store(guard->ring + (guard->seq & (kTowerRing - 1)), guard->seq, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (XE == XE_STATS) vk[p] = v;

@@ -1,6 +1,7 @@
 // Internal (non-ABI) declarations shared by the C-ABI and the kernel launchers.
 #pragma once
 #include "pv_common.h"
+#include "pv_posted.h"
 #include "../../include/azg_pv.h"
 
 #include <vector>
@@ -66,7 +67,7 @@ extern unsigned g_tower_wait_us;
 extern int g_tower_coh;        // study build only
 extern int g_board_abl;        // pv_board.hip (read by the study build only)
 extern int g_board16_split;    // pv_board16.hip
-extern int g_tower_breaker_s;  // pv_capi.hip: seconds of per-layer convs after a recovered launch
+extern int g_tower_breaker_s;  // pv_eval.hip: seconds of per-layer convs after a recovered launch
 extern int g_train_fuse_apply; // pv_train.hip
 extern int g_train_fuse_fin;
 extern int g_train_apply_grid;
@@ -79,13 +80,6 @@ constexpr int kTowerMaxBlocks = 32;
 int conv_batch_bucket(int M);
 size_t tower_sync_bytes(int nlayers, int M);
 size_t tower_prod_bytes(int nlayers, int M);
-constexpr unsigned kTowerRing = 256;          // host ring of timed-out launch numbers (power of 2)
-constexpr unsigned kTrainOvfWords = 16;       // + the train step's words (same memory): [kTrainFlag] the split-fp16
-                                              // train forward's overflow flag of the step in flight (moved into the
-                                              // gradient buffer's skip slot and cleared by heads_small_grads),
-                                              // [kTrainSkips] steps the Adam kernel skipped (azg_pv_train_status)
-constexpr unsigned kTrainFlag = 1, kTrainSkips = 2;
-constexpr unsigned kStatusWords = 2 * kTowerRing + kTrainOvfWords;
 constexpr int kTowerDiagWords = 64;           // device wait record (pv_tower.hip TowerDiag)
 constexpr unsigned kTowerWaitUs = 100000u;    // default awake-time bound of one dependency wait: 100 ms
                                               // (longest legitimate wait measured: 7.3 ms, two processes
@@ -166,21 +160,6 @@ hipError_t launch_pack_h3(const float* params, const int64_t* offs, int nl, int 
 hipError_t launch_pack_h3_dgrad(const float* params, const int64_t* offs, int nl, int C, const int* exps, void* wd16,
                                 hipStream_t st);
 
-// What one eval forward reads and writes.  `batch` counts BOARDS, here and in every host
-// function that takes an EvalCall; the kernel launchers' B / M count IMAGES (images():
-// 8 per board under SYM_MEAN8, the stem reading each board through its symmetries), and so
-// do the workspace size and the profile's board counts.
-struct EvalCall {
-    const float* x = nullptr;          // float planes [batch][3][15][15], or
-    const int8_t* boards = nullptr;    // int8 boards and players to move (x null)
-    const int8_t* players = nullptr;
-    const int8_t* syms = nullptr;      // SYM_EACH: one symmetry per board
-    int symmode = SYM_NONE;
-    int batch = 0;
-    float *probs = nullptr, *values = nullptr;
-    float *logits = nullptr, *priors = nullptr;   // optional
-    int images() const { return symmode == SYM_MEAN8 ? 8 * batch : batch; }
-};
 // azg_pv_recover's recompute of a posted launch
 struct EvalOpts {
     bool per_layer = false;    // per-layer convs (no cross-workgroup waits); posts no new launch
@@ -254,32 +233,11 @@ struct azg_pv {
     unsigned* tower_sync = nullptr;   // persistent tower: work counter, error word, tile counters
     void* tower_prod = nullptr;       // persistent tower: per-tile producer records
     unsigned* tower_diag = nullptr;   // persistent tower: wait record (kTowerDiagWords, device)
-    unsigned* ring_host = nullptr;    // timed-out launch numbers [kTowerRing], pinned + mapped (kernels post, host reads)
-    unsigned* ring_dev = nullptr;     // device alias of ring_host
-    unsigned* ovf_host = nullptr;     // H3 launches whose activations left fp16's range [kTowerRing], same memory
-    unsigned* train_ovf_dev = nullptr;   // [kTrainOvfWords] split-fp16 train forward overflow flags (device alias)
-    unsigned* ovf_dev = nullptr;
+    azg::PostedLaunches posted;       // status words, launch numbers and records, breaker (pv_posted.h)
     char* b16x = nullptr;             // board16 split exchange images [kB16SplitCap][2][image] (zeroed)
     unsigned* b16flag = nullptr;      // [kB16SplitCap][3] publish flags
     unsigned b16epoch = 0;            // split launches so far (their flag tags)
     bool b16_split = false;           // the last forward's board16 launch ran split (heads unfused)
-    unsigned seq = 0;                 // last tower launch number handed out (0 = none yet)
-    unsigned last_seq = 0;            // the last forward's launch number (0: it ran per-layer convs)
-    // what each posted launch read and wrote, by seq % kTowerRing (azg_pv_recover re-runs it)
-    struct LaunchRec {
-        unsigned seq = 0;
-        bool h3 = false;
-        int precision = AZG_PV_EVAL_EXACT;   // of the launch (the handle may have been switched since)
-        azg::EvalCall call;
-    };
-    std::vector<LaunchRec> launches;
-    uint32_t recovered = 0;           // launches recomputed per layer
-    uint32_t h3_overflows = 0;        // H3 launches recomputed with fp32 MFMA (activations beyond fp16's range)
-    // circuit breaker: a recovered launch means the dispatch did not run as one (the GPU is
-    // shared and parts of it were suspended); forwards run per-layer convs until then
-    double breaker_until = 0.0;       // steady-clock seconds
-    uint32_t breaker_trips = 0;
-    uint32_t breaker_launches = 0;    // forwards that ran per layer because of it
     int act_cap = 0;
 
     // train workspace (pv_train.hip)
@@ -307,4 +265,22 @@ int prof_begin(azg_pv* h, int cls, hipStream_t st, int64_t boards = 0);   // ret
 hipError_t prof_harvest(azg_pv* h);
 void prof_end(azg_pv* h, int pair, hipStream_t st);
 int32_t forward_eval(azg_pv* h, const EvalCall& c, hipStream_t st, const EvalOpts& o = {});
+// the shared tail of the public forwards, and azg_pv_recover's body (pv_eval.hip; arguments checked)
+int32_t run_eval(azg_pv* h, const EvalCall& c, void* stream);
+int32_t recover_eval(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream);
+
+// hipMalloc of a buffer that lives as long as the handle: azg_pv_destroy frees the list
+template <class T>
+inline hipError_t handle_malloc(azg_pv* h, T** p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) h->dev_allocs.push_back(*p);
+    return e;
+}
 }  // namespace azg
+
+#define AZG_TRY(expr, what)                                      \
+    do {                                                         \
+        hipError_t _e = (expr);                                  \
+        if (_e != hipSuccess) return azg::set_error(what, _e);   \
+    } while (0)

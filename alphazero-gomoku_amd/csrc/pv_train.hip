@@ -859,7 +859,7 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
             fx.cnt = w->fincnt;
         }
         AZG_CK(launch_conv3x3_train(C, epi, xe, in, wp, res, out, M, ex, st, nullptr, fin >= 0 ? &fx : nullptr, osc,
-                                    osc && !dmx ? h->train_ovf_dev : nullptr, dmx),
+                                    osc && !dmx ? h->posted.train_ovf_dev : nullptr, dmx),
                "train: conv3x3");
         prof_end(h, pr, st);
         return 0;
@@ -933,7 +933,7 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
             FinX fx = fin_args(fin, true);
             fx.cnt = w->fincnt;
             AZG_CK(launch_conv3x3_train(C, EPI_RAW, XE_STATS, p.z, fwd_w(ci), nullptr, out, M, ex, st, &px,
-                                        ffin ? &fx : nullptr, fwd_s(ci), fh3 ? h->train_ovf_dev : nullptr),
+                                        ffin ? &fx : nullptr, fwd_s(ci), fh3 ? h->posted.train_ovf_dev : nullptr),
                    "train: conv3x3 (fused BN apply)");
             prof_end(h, pr, st);
             if (!ffin) return fin_fwd(fin, TRAIN_BM, ntt);
@@ -1116,7 +1116,7 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
            "train: head fc wgrad");
     hipLaunchKernelGGL(heads_small_grads_kernel, dim3((HSG_OUT + 3) / 4), dim3(256), 0, st, w->dlogits, w->dhv,
                        w->dpre, w->hv, w->lossb, B, G + h->poff[h->t_pfc_b], G + h->poff[h->t_vfc1_b],
-                       G + h->poff[h->t_vfc2_w], G + h->poff[h->t_vfc2_b], losses, h->train_ovf_dev,
+                       G + h->poff[h->t_vfc2_w], G + h->poff[h->t_vfc2_b], losses, h->posted.train_ovf_dev,
                        G + h->nparams);
     AZG_CK(hipGetLastError(), "train: heads_small_grads");
     // policy_conv.weight [2][C] then value_conv.weight [C]: partial layout [t][3][C]
@@ -1216,7 +1216,7 @@ int32_t train_apply(azg_pv* h, float* exp_avg, float* exp_avg_sq, int64_t step, 
     const float bc2_sqrt = (float)std::sqrt(bc2);
     // 1024 workgroups, grid-stride: each reduces the 1024 norm partials (8 KB) itself
     const BnKeep keep{h->bn, w->bn_bak, (int)h->nbn, h->nbt, w->nbt_bak, (int)h->bn_desc.size(),
-                      h->train_ovf_dev ? h->train_ovf_dev + kTrainSkips : nullptr};
+                      h->posted.train_ovf_dev ? h->posted.train_ovf_dev + kTrainSkips : nullptr};
     const Ema ema{h->ema_params, h->ema_bn, (float)(1.0 - (double)h->ema_decay)};
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n) < 1024 ? grid_for(n) : 1024), dim3(256), 0, st, h->params,
                        h->grads, exp_avg, exp_avg_sq, n, w->npart, nb, max_norm, w->scal, total_norm, lr_bc1,

@@ -380,13 +380,13 @@ static int run(int B, int reps)
     CK(hipMalloc(&d_w, 2 * wn * 2));
     CK(hipMalloc(&d_sc, C * 4));
     CK(hipMalloc(&d_sh, C * 4));
-    CK(hipMalloc(&d_ring, kH3RingSize * 4));
+    CK(hipMalloc(&d_ring, kTowerRing * 4));
     CK(hipMemcpy(d_in, h_in.data(), act * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_res, h_res.data(), act * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_w, h_w.data(), 2 * wn * 2, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_sc, h_sc.data(), C * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(d_sh, h_sh.data(), C * 4, hipMemcpyHostToDevice));
-    CK(hipMemset(d_ring, 0, kH3RingSize * 4));
+    CK(hipMemset(d_ring, 0, kTowerRing * 4));
     CK(hipMemset(d_out, 0, act * 4));
     CK(hipMemset(d_ref, 0, act * 4));
     hipStream_t st;
@@ -435,10 +435,10 @@ static int run(int B, int reps)
         } else {
             CK(hipMemcpy(h_ref.data(), d_ref, act * 4, hipMemcpyDeviceToHost));
         }
-        unsigned ring[kH3RingSize];
+        unsigned ring[kTowerRing];
         CK(hipMemcpy(ring, d_ring, sizeof(ring), hipMemcpyDeviceToHost));
         int posted = 0;
-        for (unsigned k = 0; k < kH3RingSize; ++k) posted += ring[k] != 0;
+        for (unsigned k = 0; k < kTowerRing; ++k) posted += ring[k] != 0;
         printf("{\"C\": %d, \"B\": %d, \"variant\": \"%s\", \"tile\": \"%dx%d\", \"lds\": %zu, \"best_us\": %.2f, "
                "\"mean_us\": %.2f, \"tflops\": %.1f, \"bitwise_first\": %s, \"max_abs_diff\": %.3g, \"posted\": %d}\n",
                C, B, v.name.c_str(), v.bm, v.bn, v.lds, best * 1e3, tot / 3 * 1e3, flop / (best * 1e-3) / 1e12,

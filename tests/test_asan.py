@@ -1,6 +1,7 @@
 """Host AddressSanitizer + UBSan runs (SURVEY §5 race/sanitizer row): the native
 search (mcts_engine.cpp, whole) and the host side of the policy/value C-ABI
-(pv_capi.hip with -Xarch_host -fsanitize=address) driven through their C-ABIs by
+(pv_capi.hip and pv_eval.hip with -Xarch_host -fsanitize=address) driven through their
+C-ABIs, and the posted-launch bookkeeping (pv_posted.h) driven over a plain array, by
 csrc/asan/*.cpp.  Any sanitizer report fails the test.  CPU only (no kernel runs)."""
 import os
 import subprocess
@@ -20,7 +21,7 @@ def built():
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("driver", ["asan_mcts", "asan_pv"])
+@pytest.mark.parametrize("driver", ["asan_mcts", "asan_pv", "asan_posted"])
 def test_sanitized_driver(built, driver):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([os.path.join(built, driver)], capture_output=True, text=True, timeout=240, env=env)
