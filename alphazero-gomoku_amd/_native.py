@@ -85,6 +85,10 @@ _SIGS = {
     "azg_pv_replay_gather": (ctypes.c_int32, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P, _P]),
     "azg_pv_score_outputs": (ctypes.c_int32, [_P, _P, _P, _P, ctypes.c_int32, _P, _P, _P]),
+    "azg_pv_replay_surprise_weights": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                        ctypes.c_double, _P, ctypes.c_int32, ctypes.c_int32, _P]),
+    "azg_pv_replay_prefix": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P]),
+    "azg_pv_replay_draw": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_CLASSES = ("conv3x3", "stem", "heads", "train_conv", "train_wgrad", "train_other", "tower", "tower16", "board",

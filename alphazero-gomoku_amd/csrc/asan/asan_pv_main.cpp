@@ -163,6 +163,29 @@ int main()
         CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 4, 2, 8, &id, 1, &f, &f, &f, nullptr) != 0);
         CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 2, 8, nullptr, 1, &f, &f, &f, nullptr) != 0);
     }
+    // weighted replay sampling: likewise
+    {
+        float f = 0.f;
+        uint32_t w = 0;
+        uint64_t u = 0;
+        int64_t id = 0;
+        CHECK(azg_pv_replay_surprise_weights(nullptr, 1, 1, 1, 0.5, &w, 4, 0, nullptr) != 0);
+        CHECK(std::strstr(azg_pv_last_error(), "azg_pv_replay_surprise_weights") != nullptr);
+        CHECK(azg_pv_replay_surprise_weights(&f, 1, 1, 1, 1.5, &w, 4, 0, nullptr) != 0);
+        CHECK(azg_pv_replay_surprise_weights(&f, 0, 1, 1, 0.5, &w, 4, 0, nullptr) != 0);
+        CHECK(azg_pv_replay_surprise_weights(&f, 1, 5, 5, 0.5, &w, 4, 0, nullptr) != 0);
+        CHECK(azg_pv_replay_surprise_weights(&f, 1, 2, 1, 0.5, &w, 4, 0, nullptr) != 0);
+        CHECK(azg_pv_replay_surprise_weights(&f, 1, 1, 1, 0.5, &w, 4, 4, nullptr) != 0);
+        CHECK(azg_pv_replay_prefix(nullptr, 4, 0, 2, &u, nullptr) != 0);
+        CHECK(std::strstr(azg_pv_last_error(), "azg_pv_replay_prefix") != nullptr);
+        CHECK(azg_pv_replay_prefix(&w, 4, 0, 5, &u, nullptr) != 0);
+        CHECK(azg_pv_replay_prefix(&w, 4, 4, 2, &u, nullptr) != 0);
+        CHECK(azg_pv_replay_draw(&u, 2, 8, nullptr, 1, &id, nullptr) != 0);
+        CHECK(std::strstr(azg_pv_last_error(), "azg_pv_replay_draw") != nullptr);
+        CHECK(azg_pv_replay_draw(&u, 0, 8, &u, 1, &id, nullptr) != 0);
+        CHECK(azg_pv_replay_draw(&u, 2, 3, &u, 1, &id, nullptr) != 0);
+        CHECK(azg_pv_replay_draw(&u, 2, 8, &u, 0, &id, nullptr) != 0);
+    }
     // tuning keys round-trip (previous value returned)
     const int prev = azg_pv_set_tuning(AZG_PV_TUNE_TOWER_MODE, 0);
     CHECK(azg_pv_set_tuning(AZG_PV_TUNE_TOWER_MODE, prev) == 0);

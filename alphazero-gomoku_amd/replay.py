@@ -15,6 +15,13 @@ Image numbering makes the two buffers interchangeable: image i of this buffer is
 element i of the host deque (position i // 8 in ring order, symmetry i % 8), and
 random.sample picks by index from (len, k) alone, so under the same random.seed
 ``sample`` returns the host buffer's batch bit for bit.
+
+Opt-in, the ring also carries one WEIGHT per position (``add_positions(...,
+surprise=...)``, ``set_weights``) and ``sample_weighted`` draws positions in proportion to
+it on the device (csrc/pv_replay_weights.hip): weights are integers, 2**16 quanta per unit
+of weight, so their running sums are exact and the draw is an integer function of the
+random words -- tests/replay_weights_reference.py reproduces every id in Python integers.
+A buffer that never sees a weighted call allocates and does nothing new.
 """
 from __future__ import annotations
 
@@ -29,6 +36,8 @@ from selfplay import ReplayBuffer
 
 _N = 15
 _PIX = _N * _N
+QUANTA = 1 << 16          # quanta per unit of weight (include/azg_pv.h)
+MAX_WEIGHT = 1 << 15      # set_weights' bound: below 2**31 quanta
 
 
 def _images(S: np.ndarray, P: np.ndarray):
@@ -76,19 +85,41 @@ class DeviceReplayBuffer:
         self.zs = torch.zeros(self.cap_pos, dtype=torch.float32, device=self.device)
         self.head = 0     # slot of the oldest position
         self.count = 0    # positions held
+        # surprise weighting: nothing of it exists until the first weighted call
+        self.weights = None        # [cap_pos] uint32 quanta, by slot (a view of _wq)
+        self._wq = None            # the same memory as int32 (quanta < 2**31), for torch's copies and fills
+        self._prefix = None        # [cap_pos] running sums of the weights in ring order (uint64 bits in int64)
+        self._prefix_ok = False    # False whenever the weights or the ring have moved since the last scan
 
     def __len__(self) -> int:
         return self.count * self.nsym
 
     # ---------------------------------------------------------------- writing
-    def add_positions(self, examples) -> None:
+    def add_positions(self, examples, surprise=None, mix: float = 0.5) -> None:
         """Canonical (state [3,15,15], pi [225], z) tuples, as
         selfplay_games(use_symmetries=False) returns them; the oldest positions are
-        overwritten (= the deque's eviction of whole groups of nsym images)."""
+        overwritten (= the deque's eviction of whole groups of nsym images).
+
+        surprise (optional; one value per example: a device fp32 tensor [n] or [n,8] -- score
+        records, field 0 = the policy KL, used in place -- or a host array [n]) gives the new
+        positions the weights  (1 - mix) + mix * n * s_i / sum(s)  (azg_pv_replay_surprise_weights:
+        non-finite and non-positive surprises count as 0; all of them 0: every weight 1), in
+        quanta of 2**-16; the sum runs over all n examples passed even where only the newest
+        cap_pos survive.  Without it the new positions weigh 1.0 once the buffer has weights."""
         examples = list(examples)
         if not examples:
             return
         S, P, Z = _stack(examples)
+        n_all = len(S)
+        if surprise is not None:
+            if not 0.0 <= float(mix) <= 1.0:
+                raise ValueError(f"mix must be in [0, 1], got {mix!r}")
+            if not torch.is_tensor(surprise):
+                surprise = torch.from_numpy(np.ascontiguousarray(surprise, dtype=np.float32))
+            if tuple(surprise.shape) not in ((n_all,), (n_all, 8)) or surprise.dtype != torch.float32:
+                raise ValueError(f"surprise must be float32 of shape [{n_all}] or [{n_all}, 8], got "
+                                 f"{surprise.dtype} {tuple(surprise.shape)}")
+            surprise = surprise.to(self.device).contiguous()
         p0, p1 = S[:, 0], S[:, 1]
         if not (((p0 == 0) | (p0 == 1)).all() and ((p1 == 0) | (p1 == 1)).all()):
             raise ValueError("state planes 0 / 1 must hold 0 or 1")
@@ -117,10 +148,61 @@ class DeviceReplayBuffer:
                 self.pis[at:at + hi - lo].copy_(h_pi[lo:hi], non_blocking=True)
                 self.zs[at:at + hi - lo].copy_(h_z[lo:hi], non_blocking=True)
                 self.stones[at:at + hi - lo].copy_(h_st[lo:hi], non_blocking=True)
+        if surprise is not None:
+            self._ensure_weights()
+            with torch.cuda.device(self.device):
+                check(self.lib.azg_pv_replay_surprise_weights(
+                    ptr(surprise), 8 if surprise.dim() == 2 else 1, n, n_all, float(mix), ptr(self._wq), self.cap_pos,
+                    tail, torch.cuda.current_stream(self.device).cuda_stream), self.lib)
+        elif self._wq is not None:     # eviction takes the old weights with the old positions
+            self._wq[tail:tail + first].fill_(QUANTA)
+            self._wq[0:n - first].fill_(QUANTA)
+        self._prefix_ok = False
         over = self.count + n - self.cap_pos
         if over > 0:
             self.head = (self.head + over) % self.cap_pos
         self.count = min(self.count + n, self.cap_pos)
+
+    # ---------------------------------------------------------------- weights
+    def _ensure_weights(self) -> None:
+        if self._wq is None:   # every position held so far weighs 1.0
+            self._wq = torch.full((self.cap_pos,), QUANTA, dtype=torch.int32, device=self.device)
+            self.weights = self._wq.view(torch.uint32)
+            self._prefix = torch.zeros(self.cap_pos, dtype=torch.int64, device=self.device)
+            self._prefix_ok = False
+
+    def set_weights(self, w) -> None:
+        """Weights of the positions held, a host float array [count] in ring order (oldest
+        first): finite, >= 0, each < 32768, sum > 0; stored rounded to quanta of 2**-16."""
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        if len(w) != self.count or self.count < 1:
+            raise ValueError(f"{len(w)} weights for {self.count} positions")
+        if not np.isfinite(w).all() or (w < 0).any() or (w >= MAX_WEIGHT).any() or not w.sum() > 0:
+            raise ValueError(f"weights must be finite, in [0, {MAX_WEIGHT}) and not all zero")
+        q = np.rint(w * QUANTA).astype(np.int64)
+        if not q.sum() > 0:
+            raise ValueError("every weight rounds to zero quanta (one quantum is 2**-16)")
+        self._ensure_weights()
+        stage = torch.empty(self.count, dtype=torch.int32, pin_memory=True)
+        stage.numpy()[...] = q
+        first = min(self.count, self.cap_pos - self.head)
+        self._wq[self.head:self.head + first].copy_(stage[:first], non_blocking=True)
+        self._wq[0:self.count - first].copy_(stage[first:], non_blocking=True)
+        self._prefix_ok = False
+
+    def get_weights(self) -> np.ndarray:
+        """The weights of the positions held, float64 [count] in ring order (all 1.0 for a
+        buffer without weights).  Synchronises."""
+        if self._wq is None:
+            return np.ones(self.count, dtype=np.float64)
+        order = (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
+        return self._wq[order].cpu().numpy().astype(np.float64) / QUANTA
+
+    def effective_sample_size(self) -> float:
+        """(sum w)^2 / sum w^2 over the positions held: how many equally weighted positions
+        the weighted draw is worth.  Synchronises: for logging."""
+        w = self.get_weights()
+        return float(w.sum() ** 2 / (w * w).sum()) if len(w) and w.any() else 0.0
 
     # --------------------------------------------------------------- sampling
     def draw_ids(self, batch_size: int) -> list:
@@ -146,6 +228,46 @@ class DeviceReplayBuffer:
                                                 self.head, self.count, self.nsym, ptr(d_ids), batch_size,
                                                 ptr(s), ptr(p), ptr(z),
                                                 torch.cuda.current_stream(dev).cuda_stream), self.lib)
+        return s, p, z
+
+    def draw_words(self, batch_size: int) -> np.ndarray:
+        """sample_weighted's default random words, uint64 [batch, 2]: two
+        random.getrandbits(64) per element in element order, so random.seed governs them
+        as it governs draw_ids."""
+        return np.array([random.getrandbits(64) for _ in range(2 * batch_size)], dtype=np.uint64).reshape(batch_size, 2)
+
+    def sample_weighted(self, batch_size: int, rnd=None):
+        """``sample``'s tensors for a batch drawn WITH replacement, each position in proportion
+        to its weight and, with nsym = 8, one of its 8 images uniformly; no host sync and no
+        host copy of the weights.  rnd (optional uint64 [batch, 2]): word 0 of an element
+        picks the position (azg_pv_replay_draw), the low 3 bits of word 1 the image.  A
+        buffer without weights draws as if every weight were 1.0 (and has weights from then
+        on).  The running sums are scanned again only after the weights or the ring moved."""
+        if batch_size < 1 or self.count < 1:
+            raise ValueError(f"a batch of {batch_size} from {self.count} positions")
+        rnd = self.draw_words(batch_size) if rnd is None else np.asarray(rnd)
+        if rnd.dtype != np.uint64 or rnd.shape != (batch_size, 2):
+            raise ValueError(f"rnd must be uint64 [{batch_size}, 2], got {rnd.dtype} {rnd.shape}")
+        self._ensure_weights()
+        dev = self.device
+        h_rnd = torch.empty((batch_size, 2), dtype=torch.int64, pin_memory=True)
+        h_rnd.numpy()[...] = rnd.view(np.int64)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if not self._prefix_ok:
+                check(self.lib.azg_pv_replay_prefix(ptr(self._wq), self.cap_pos, self.head, self.count,
+                                                    ptr(self._prefix), st), self.lib)
+                self._prefix_ok = True
+            d_rnd = h_rnd.to(dev, non_blocking=True)
+            d_ids = torch.empty(batch_size, dtype=torch.int64, device=dev)
+            check(self.lib.azg_pv_replay_draw(ptr(self._prefix), self.count, self.nsym, ptr(d_rnd), batch_size,
+                                              ptr(d_ids), st), self.lib)
+            s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
+            p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
+            z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
+            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(self.pis), ptr(self.zs), self.cap_pos,
+                                                self.head, self.count, self.nsym, ptr(d_ids), batch_size,
+                                                ptr(s), ptr(p), ptr(z), st), self.lib)
         return s, p, z
 
     # ------------------------------------------------------------ host format

@@ -178,6 +178,17 @@ def _score_new_games(model, examples, limit: int) -> Optional[dict]:
     return model.score_batch(*_stack_examples(examples)) if examples else None
 
 
+def _score_surprise(model, examples) -> torch.Tensor:
+    """The [n,8] device score records of ALL of examples under the model as it is now (field 0:
+    the KL between the search's policy target and the net's policy), scored as
+    _score_new_games scores but kept on the device."""
+    s, t, z = _stack_examples(examples)
+    dev = model.engine.device
+    _, records = model.score_sums_device(torch.from_numpy(s).to(dev), torch.from_numpy(t).to(dev),
+                                         torch.from_numpy(z).to(dev), per_board=True, max_batch=4096)
+    return records
+
+
 def _score_line(tag: str, d: Optional[dict]) -> str:
     if d is None:
         return f"  new games {tag}: no examples on this rank"
@@ -196,7 +207,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     device_buffer: bool = False, leaf_symmetry=None, eval_symmetry=None,
                     selfplay_precision: Optional[str] = None, score_new_games: bool = False,
                     score_max_examples: int = 4096, history: Optional[list] = None,
-                    ema_decay: Optional[float] = None, **reference_worker_kwargs):
+                    ema_decay: Optional[float] = None, surprise_weight: Optional[float] = None,
+                    **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -232,7 +244,28 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     and moved by every train step inside the Adam kernel.  Gating plays the AVERAGE
     (model_candidate.ema_model()) against model_best, and on acceptance model_best takes the
     averaged weights with the candidate's optimiser state; the raw weights only train.
-    history entries carry "ema_decay".  None, the default, makes no EMA call."""
+    history entries carry "ema_decay".  None, the default, makes no EMA call.
+
+    surprise_weight (None or in [0, 1]; needs device_buffer=True): KataGo's policy surprise
+    weighting.  Before this rank's fresh examples enter the buffer the candidate scores ALL
+    of them in "exact" precision (score_sums_device, chunks of 4096; the records stay on the
+    device) and their policy KL becomes their sampling weight,
+    (1 - surprise_weight) + surprise_weight * n * KL_i / sum(KL)
+    (DeviceReplayBuffer.add_positions(surprise=..., mix=...)); batches are then drawn in
+    proportion to the weights on the device (sample_weighted: with replacement, governed by
+    random.seed).  Old positions keep the weight they entered with.  The loss is not
+    reweighted.  history entries carry "surprise_weight" and "buffer_ess" (the buffer's
+    effective sample size in positions, None when off), and the weights are kept beside the
+    buffer pickle in replay_weights_latest{suffix}.npy, applied on start when they match the
+    loaded buffer's position count (otherwise every loaded position weighs 1.0).  None, the
+    default, makes none of these calls: the loop samples uniformly as before."""
+    if surprise_weight is not None:
+        if isinstance(surprise_weight, bool) or not isinstance(surprise_weight, (int, float, np.floating, np.integer)) \
+                or not 0.0 <= float(surprise_weight) <= 1.0:
+            raise ValueError(f"surprise_weight must be None or a number in [0, 1], got {surprise_weight!r}")
+        if not device_buffer:
+            raise ValueError("surprise_weight needs device_buffer=True (the host ReplayBuffer carries no weights)")
+        surprise_weight = float(surprise_weight)
     if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be None or in [0, 1), got {ema_decay!r}")
     if selfplay_precision not in (None, "exact", "fp16"):
@@ -263,6 +296,11 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         buffer = new_device_buffer(load_replay_buffer(buffer_path, capacity=buffer_size), buffer_size, device)
     else:
         buffer = load_replay_buffer(buffer_path, capacity=buffer_size) or ReplayBuffer(capacity=buffer_size)
+    weights_path = os.path.join(model_dir, f"replay_weights_latest{suffix}.npy")
+    if surprise_weight is not None and buffer.count and os.path.exists(weights_path):
+        saved = np.load(weights_path, allow_pickle=False)
+        if saved.shape == (buffer.count,):   # the sidecar of another buffer: start from 1.0 instead
+            buffer.set_weights(saved)
     # a device buffer of single images (nsym = 1: a loaded buffer that is not whole groups
     # of 8) takes the expanded examples like the deque; otherwise it forms the images itself
     host_symmetries = not device_buffer or buffer.nsym == 1
@@ -291,7 +329,10 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             score_before = _score_new_games(model_candidate, examples, score_max_examples)
             if main:
                 print(_score_line("before training", score_before))
-        if device_buffer:
+        if surprise_weight is not None and examples:
+            kl = _score_surprise(model_candidate, examples)
+            buffer.add_positions(examples, surprise=kl, mix=surprise_weight)
+        elif device_buffer:
             buffer.add_positions(examples)
         else:
             buffer.add(examples)
@@ -307,7 +348,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             for epoch in range(epochs_per_iter):
                 te = time.time()
                 for _ in range(n_batches):
-                    s, p, z = buffer.sample(batch_size)
+                    s, p, z = (buffer.sample(batch_size) if surprise_weight is None
+                               else buffer.sample_weighted(batch_size))
                     if device_buffer:   # the synchronous step: a skipped step is redone as on the host path
                         loss_info = model_candidate.train_batch_device(s, p, z, epochs=1)
                     else:
@@ -323,7 +365,9 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                 print(_score_line("after training", score_after))
         if history is not None:
             history.append({"iteration": it, "new_games_before": score_before, "new_games_after": score_after,
-                            "last_train_loss": loss_info, "ema_decay": ema_decay})
+                            "last_train_loss": loss_info, "ema_decay": ema_decay,
+                            "surprise_weight": surprise_weight,
+                            "buffer_ess": None if surprise_weight is None else buffer.effective_sample_size()})
 
         te = time.time()
         # with EMA on, the gated net is the average of the candidate's weights, not its last step
@@ -360,6 +404,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             model_best.save(path)
             print(f" saved snapshot: {path}")
         save_replay_buffer(buffer.to_host() if device_buffer else buffer, buffer_path)
+        if surprise_weight is not None:
+            np.save(weights_path, buffer.get_weights())
         if main:
             print(f"iteration {it} done in {(time.time() - t0) / 60:.2f} min; winners {winners}")
     if main:

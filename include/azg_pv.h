@@ -222,6 +222,53 @@ int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, const float
                              const int64_t* ids, int32_t batch,
                              float* x, float* pi_out, float* z_out, void* stream);
 
+/* Surprise-weighted sampling from the same ring (handle-free; three entry points beside
+ * azg_pv_replay_gather, which they feed and do not change).  Every position carries a
+ * weight in FIXED POINT: weights [cap_pos] uint32, one unit of weight = 65536 quanta, at
+ * most 2^31 - 1 quanta.  Sums of integers are exact in any order and the draw is an integer
+ * function of the random words, so a host restatement in integers gives the same ids.
+ *
+ * azg_pv_replay_surprise_weights: weights of freshly added positions from their "surprise"
+ * (KataGo's policy surprise weighting: field AZG_PV_SCORE_KL of azg_pv_score_outputs'
+ * records, below).  surprise (device fp32) holds n_sum records `stride` floats apart; record
+ * i is sanitised to s_i = surprise[i*stride] if finite and > 0, else 0, and S = sum of ALL
+ * n_sum s_i in fp64, in an order fixed by n_sum alone (one workgroup: thread i adds i,
+ * i + 256, ... in increasing order, then a fixed tree; no atomics).  In fp64, in this
+ * operation order,  w_i = (1 - mix) + mix * n_sum * s_i / S   (w_i = 1 when S == 0): a
+ * uniform share plus a share in proportion to the surprise, mean 1 over the n_sum records.
+ * Only the NEWEST n records (i in [n_sum - n, n_sum), n <= n_sum: the ones that survive in a
+ * ring of cap_pos when more were added at once) are written, record n_sum - n + k to
+ * weights[(at + k) % cap_pos], as  min(2^31 - 1, llrint(w_i * 65536))  quanta.  The sum
+ * range is thus given by the one extra length n_sum, not by a second pointer.
+ * Checked before any device call: null surprise or weights, mix outside [0, 1] (NaN
+ * included), stride < 1, cap_pos < 1, n outside [1, cap_pos], n_sum < n, at outside
+ * [0, cap_pos).  One launch of one workgroup.
+ *
+ * azg_pv_replay_prefix: prefix[j] = sum over i <= j of weights[(head + i) % cap_pos], uint64,
+ * for j < count -- running sums in ring order (oldest position first).  A three-pass scan
+ * (per-thread chunks, wavefront scan, LDS across waves; tile totals; carried offsets) that
+ * uses `prefix` itself as its only workspace.  Call it when the weights or the ring have
+ * changed, not per batch.  Checked: null weights or prefix, cap_pos < 1, count outside
+ * [1, cap_pos], head outside [0, cap_pos).  One launch up to 1024 positions, else three.
+ *
+ * azg_pv_replay_draw: batch image ids, with replacement.  rnd [batch][2] (device uint64) are
+ * uniform random words.  With total = prefix[count - 1], element k takes
+ * t = floor(rnd[2k] * total / 2^64) (the high half of the 128-bit product), j = the smallest
+ * index with prefix[j] > t (binary search), and ids[k] = j * nsym + (nsym == 8 ?
+ * rnd[2k+1] & 7 : 0) -- azg_pv_replay_gather's image numbers.  A position is chosen with
+ * probability weight / total up to 2^-64 * count; a position of weight 0 never.  With
+ * total == 0 (no weight anywhere: the caller's error) every id is position count - 1: ids
+ * never leave the ring.  Checked: null prefix, rnd or ids, count < 1, nsym not 1 or 8,
+ * batch < 1.  One launch.
+ * All three are asynchronous on `stream` and allocate nothing. */
+int32_t azg_pv_replay_surprise_weights(const float* surprise, int32_t stride, int32_t n, int32_t n_sum,
+                                       double mix, uint32_t* weights, int32_t cap_pos, int32_t at,
+                                       void* stream);
+int32_t azg_pv_replay_prefix(const uint32_t* weights, int32_t cap_pos, int32_t head, int32_t count,
+                             uint64_t* prefix, void* stream);
+int32_t azg_pv_replay_draw(const uint64_t* prefix, int32_t count, int32_t nsym, const uint64_t* rnd,
+                           int32_t batch, int64_t* ids, void* stream);
+
 /* Score eval-forward outputs against targets without a train step (handle-free): the two
  * loss terms of the reference's train_batch -- KLDivLoss(batchmean) on log_softmax(logits)
  * and MSELoss on the value, network.py:162-163,216-219 -- per board and summed, plus policy
