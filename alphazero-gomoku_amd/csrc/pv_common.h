@@ -46,7 +46,7 @@ __device__ __forceinline__ int pad_off(int m, int C) {
 // square (y, x): image[y][x] = board[sym_src(y, x, s)].  With r = np.rot90(a, k),
 // r[y][x] = a[x][n-1-y] for k = 1 (and its powers); np.flip(r, columns)[y][x] = r[y][n-1-x].
 // Shared by the replay gather (pv_replay.hip) and the symmetric leaf evaluation (the
-// board-input stems of pv_conv.hip read through it, pv_heads.hip stores through it).
+// board-input stems of pv_stem.hip read through it, pv_heads.hip stores through it).
 __host__ __device__ __forceinline__ int sym_src(int y, int x, int s)
 {
     constexpr int n = BOARD;

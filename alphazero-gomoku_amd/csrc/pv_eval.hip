@@ -313,12 +313,10 @@ static int32_t per_layer_tower(azg_pv* h, int images, hipStream_t st, const Towe
     const float* scale = p.h3 ? h->scale16 : h->scale;
     auto conv = [&](int l, int epi, const float* in, const float* resid, float* dst) {
         const int o = h->conv_bn_off[l];
-        const float* w = wp + (size_t)l * 9 * C * C;
+        const ConvCall cc{in, wp + (size_t)l * 9 * C * C, scale + o, h->shift + o, resid, dst, M, st};
         const int pr = prof_begin(h, AZG_PROF_CONV3X3, st, images);
-        const hipError_t e =
-            p.h3 ? launch_conv3x3_h3(shape, C, epi, in, w, scale + o, h->shift + o, resid, dst, M, st, h->posted.ovf_dev,
-                                     p.seq)
-                 : launch_conv3x3(C, epi, in, w, scale + o, h->shift + o, resid, dst, M, st);
+        const hipError_t e = p.h3 ? launch_conv3x3_h3(shape, C, epi, cc, h->posted.ovf_dev, p.seq)
+                                  : launch_conv3x3(C, epi, cc);
         if (e == hipSuccess) prof_end(h, pr, st);
         return e;
     };
@@ -346,6 +344,8 @@ static int32_t stem_and_tower(azg_pv* h, const EvalCall& c, hipStream_t st, cons
     if (p.variant != 0 && h->NB > 0) return tile_tower(h, c.images(), st, p, out);
     return per_layer_tower(h, c.images(), st, p, out);
 }
+
+int g_tower_mode = 2;   // 0 per-layer launches, 1 persistent tower, 2 tuned per batch bucket
 
 // Tower variant per (C, blocks, batch bucket): g_tower_mode 0 = per-layer launches,
 // 1 = persistent tower with shape g_tower_shape, 2 = timed on first use of the

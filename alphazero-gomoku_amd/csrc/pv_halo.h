@@ -68,15 +68,59 @@ constexpr int halo_span(int BM)
 // scale / shift)
 constexpr int pro_params(int PRO) { return PRO != 0 ? 2 : 0; }
 
+// The body variants of halo_tile: its template parameter VAR is a mask of these bits (an
+// int, so the kernels' names carry the plain number).  Within one arithmetic (fp32 MFMA,
+// or split-fp16 with three / four products) every VAR computes bitwise-identical results.
+enum HaloVar : int {
+    HV_BOARD_SWZ = 1,    // halo rows swizzled on the padded board position (conflict-free fragment reads), unpadded epilogue tile
+    HV_W_AHEAD2 = 2,     // weights staged two chunks ahead
+    HV_LDS_DMA = 4,      // LDS-DMA staging (halo_mainloop_glds)
+    HV_EARLY_EPI = 8,    // epilogue loads issued before the LDS pass
+    HV_BUF_SC1 = 16,     // buffer-resource operand addressing with sc1 loads, valid at one workgroup per CU only
+    HV_BUF = 32,         // buffer-resource addressing with the default cache policy
+    HV_H3 = 64,          // split-fp16 (H3): fp32-equivalent products from three fp16 MFMAs
+    HV_H3_LOLO = 128,    // H3 with the fourth, lo x lo product
+    HV_H3_TILE = 256,    // read by pv_tower.hip only, never by halo_tile: the tower's body is h3_tile (pv_h3.h)
+};
+constexpr int HV_ANY_BUF = HV_BUF_SC1 | HV_BUF;   // operands (halo rows, weights) through buffer resources
+
+// The bodies the product launches.
+// Train convs.  The board-keyed body (kHaloTower256) measured equal for the prologue-free
+// train convs: 2.865-2.869 vs 2.866-2.874 ms at 6x128 and within noise at 10x256.
+constexpr int kHaloTrain = HV_BUF;                                              // 32
+// C = 256 tower: 128x64 tile 90.0 vs 86.4 % of peak at B = 512 against kHaloTrain's body,
+// slower at C = 128 (89.5 vs 91.2 % at B = 3456), which keeps HV_BUF alone (pv_tower.hip).
+constexpr int kHaloTower256 = HV_BUF | HV_BOARD_SWZ;                            // 33
+// H3 eval, per layer and in the tower: the fastest form (+10 % over HV_H3 | HV_BUF per
+// layer at 128 boards, scripts/h3_tune_study.py; 3.8-4.8 % over the row-keyed form in the
+// tower, whose fragment reads conflict at board-row ends, profiles/r5_h3_study.md).
+constexpr int kHaloH3Eval = HV_H3 | HV_BUF | HV_W_AHEAD2 | HV_BOARD_SWZ;        // 99
+constexpr int kHaloH3EvalRowKeyed = HV_H3 | HV_BUF | HV_W_AHEAD2;               // 98 (key 20 = 0)
+// Train H3 convs: three products (keys 49 / 50 = 1) or four (= 2; key 49's default).
+constexpr int kHaloH3Train = HV_H3 | HV_BUF | HV_BOARD_SWZ;                     // 97
+constexpr int kHaloH3Train4 = kHaloH3Train | HV_H3_LOLO;                        // 225
+// Tower shape 12: h3_tile, 128x128 as 4 waves of 64x64, bitwise equal to kHaloH3Eval.
+constexpr int kHaloH3TileTower = kHaloH3Eval | HV_H3_TILE;                      // 355
+
+// XCD-aware tile order: workgroup L of nt is dispatched to XCD L % 8, so give each XCD a
+// contiguous run of logical tiles (the N tiles of one M tile adjacent, then neighbouring M
+// tiles): the input halo rows and the other N tiles' A rows are then L2 hits on the same
+// XCD instead of fabric re-reads.  Returns the logical tile of workgroup L.
+__device__ __forceinline__ int xcd_tile(int L, int nt)
+{
+    const int xcd = L & 7, q8 = nt >> 3, r8 = nt & 7;
+    return xcd * q8 + min(xcd, r8) + (L >> 3);
+}
+
 // LDS: halo rows [HR][32] + two weight chunks [2][BN][32] (register staging), or
-// two halo buffers [2][HRG][32] + [2][BN][32] (LDS-DMA staging, VAR bit 4); the
+// two halo buffers [2][HRG][32] + [2][BN][32] (HV_LDS_DMA); the
 // epilogue reuses it as a [BM][ELD] tile.
 template <int C, int BN, int WM, int TM, int NW, int VAR = 0, int PRO = 0>
 constexpr int halo_lds_bytes()
 {
     using T = ConvTile<C, BN, WM, TM, NW>;
     const int hrg = (halo_span(T::BM) + 7) / 8 * 8;
-    const int staging = (VAR & 4) ? (2 * hrg + ((VAR & 2) ? 3 : 2) * BN) * T::BK * 4
+    const int staging = (VAR & HV_LDS_DMA) ? (2 * hrg + ((VAR & HV_W_AHEAD2) ? 3 : 2) * BN) * T::BK * 4
                                   : ((halo_span(T::BM) + T::RPP - 1) / T::RPP * T::RPP + 2 * BN) * T::BK * 4 +
                                         pro_params(PRO) * C * 4;
     const int epilogue = T::BM * (BN + 8) * 4;
@@ -523,7 +567,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<
     }
 }
 
-// Main loop with LDS-DMA staging (VAR bit 4): every operand reaches LDS through
+// Main loop with LDS-DMA staging (HV_LDS_DMA): every operand reaches LDS through
 // global_load_lds_dwordx4 (one wave-instruction = 1 KiB = 8 rows of 128 B, written
 // lane-linearly; the slot swizzle is applied to each lane's SOURCE address, and the
 // fragment reads use the same swizzle -- cdna_hip_programming.md §5.4 rule 21), so
@@ -549,11 +593,11 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
     constexpr int NBP = BN / 8;               // weight pieces per chunk
     constexpr int NBW = (NBP + NW - 1) / NW;
     constexpr int NCHK = 9 * CG;
-    constexpr bool VSWZ = (VAR & 1) != 0;
-    // PF2 (VAR bit 2): three weight buffers, chunk j+2 issued at the top of chunk j and
+    constexpr bool VSWZ = (VAR & HV_BOARD_SWZ) != 0;
+    // PF2 (HV_W_AHEAD2): three weight buffers, chunk j+2 issued at the top of chunk j and
     // kept in flight across the chunk-end barrier (raw s_barrier + counted vmcnt
     // instead of __syncthreads, whose fence drains every DMA)
-    constexpr bool PF2 = (VAR & 2) != 0;
+    constexpr bool PF2 = (VAR & HV_W_AHEAD2) != 0;
     constexpr int NWB = PF2 ? 3 : 2;
     constexpr int NPF = NP / NW;              // taps at which EVERY wave issues a halo piece
     static_assert(!PF2 || NBP % NW == 0, "counted waits need the same weight pieces per wave");
@@ -739,11 +783,11 @@ __device__ __forceinline__ void halo_tile(
     const FinX& fx = FinX{}, const H3Guard& guard = H3Guard{})
 {
     using T = ConvTile<C, BN_, WM_, TM_, NW_>;
-    if constexpr ((VAR & 4) != 0) {   // LDS-DMA staging
+    if constexpr ((VAR & HV_LDS_DMA) != 0) {
         f32x16 acc[TM_][T::TN];
         halo_mainloop_glds<C, BN_, WM_, TM_, NW_, VAR>(in, wp, M, m0, n0, smem, acc);
-        halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, ABL, T::BN, (VAR & 8) != 0>(acc, scale, shift, resid, out,
-                                                                                   out_rs, M, m0, n0, smem);
+        halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, ABL, T::BN, (VAR & HV_EARLY_EPI) != 0>(
+            acc, scale, shift, resid, out, out_rs, M, m0, n0, smem);
         return;
     }
     constexpr int RPP = T::RPP;
@@ -756,15 +800,14 @@ __device__ __forceinline__ void halo_tile(
     static_assert(RPP % 16 == 0, "halo staging rows must keep the row swizzle");
     static_assert(H_LD <= 9, "halo loads are spread over the 9 taps");
     static_assert(PRO == PRO_NONE || H_LD <= 8, "the operand prologue of a row runs one tap after its load");
-    static_assert(PRO == PRO_NONE || (((VAR & ~193) == 0 || (VAR & ~193) == 32) && ABL == 0),
+    constexpr int kProBits = HV_H3 | HV_H3_LOLO | HV_BOARD_SWZ;   // what a prologue body may add to 0 / HV_BUF
+    static_assert(PRO == PRO_NONE || (((VAR & ~kProBits) == 0 || (VAR & ~kProBits) == HV_BUF) && ABL == 0),
                   "operand prologue: register staging only");
-    // VAR (A/B studies; the product uses 0, measured fastest): bit 1 = halo rows
-    // swizzled on the padded board position (conflict-free fragment reads) and an
-    // unpadded epilogue tile; bit 2 = weights staged two chunks ahead; bit 4 = LDS-DMA
-    // staging (halo_mainloop_glds); bit 8 = epilogue loads issued before the LDS pass.  Every VAR computes bitwise-identical results.
-    constexpr bool VSWZ = (VAR & 1) != 0;
-    constexpr bool BPF2 = (VAR & 2) != 0;
-    // H3 (VAR bit 64, eval only): fp32-equivalent products from three fp16 MFMAs.  Every
+    // VAR: a mask of HaloVar bits (above, with the combinations the product launches; the
+    // per-layer fp32 convs use 0, key 22 = 1 HV_BOARD_SWZ).
+    constexpr bool VSWZ = (VAR & HV_BOARD_SWZ) != 0;
+    constexpr bool BPF2 = (VAR & HV_W_AHEAD2) != 0;
+    // H3 (HV_H3): fp32-equivalent products from three fp16 MFMAs.  Every
     // operand x is split into hi = fp16(x) and lo = fp16(x - hi) (x = hi + lo to 2^-22 of
     // x, or 3e-8 absolute below fp16's normal range); a K16 step is acc += lo_a hi_b +
     // hi_a lo_b + hi_a hi_b (v_mfma_f32_32x32x16_f16: exact 22-bit products, fp32
@@ -773,7 +816,7 @@ __device__ __forceinline__ void halo_tile(
     // swizzles are unchanged.  Halo rows are split while staged; weights are packed split
     // (and scaled by a per-layer power of two so their lo parts stay normal,
     // pv_pack.hip pack_h3; the epilogue's BN scale carries the inverse).
-    constexpr bool H3 = (VAR & 64) != 0;
+    constexpr bool H3 = (VAR & HV_H3) != 0;
     // train forward (EPI_RAW + XE_STATS, PRO): BN-normalised inputs; the raw output is
     // multiplied by `scale` (2^-e of the layer) in the epilogue.  Dgrad (EPI_RAW / EPI_ADD +
     // XE_BNBWD, key 50): the input gradient is not normalised -- it is staged times 2^k from
@@ -828,11 +871,11 @@ __device__ __forceinline__ void halo_tile(
     // are fully unrolled: the rb1 = rb2 hand-over is a register renaming, not a move)
     f32x4 rh[H_LD], rb1[B_LD], rb2[B_LD];
     f32x4 rr[PRO == PRO_BN_RES ? H_LD : 1];
-    // VAR bit 16 (persistent tower at ONE workgroup per CU): halo rows are produced
+    // HV_BUF_SC1 (persistent tower at ONE workgroup per CU): halo rows are produced
     // inside the launch by other CUs; every load of them is an sc1 buffer load (L1
     // bypassed) in place of the consumer's acquire -- row 1 of the microarch guide's
     // measured hand-off table, valid only at one workgroup per CU (pv_tower.hip).
-    // VAR bit 32: the same buffer-resource addressing (32-bit offsets: fewer VGPRs than
+    // HV_BUF: the same buffer-resource addressing (32-bit offsets: fewer VGPRs than
     // 64-bit pointers) with the default cache policy, behind the consumer's acquire.
     const __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), (short)0,
                                                                           0x7fffffff, 0x00020000);
@@ -850,26 +893,26 @@ __device__ __forceinline__ void halo_tile(
         if constexpr (HPRED) {
             if (hbase + sr + RPP * i > hmax) return;
         }
-        if constexpr ((VAR & 48) != 0)
+        if constexpr ((VAR & HV_ANY_BUF) != 0)
             rh[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rs, (hsrc[i] + cg * BK) * 4, 0,
-                                                                                    (VAR & 16) ? 16 : 0));
+                                                                                    (VAR & HV_BUF_SC1) ? 16 : 0));
         else
             rh[i] = *(const f32x4*)(in + hsrc[i] + cg * BK);
         if constexpr (PRO == PRO_BN_RES) {
-            if constexpr ((VAR & 32) != 0)
+            if constexpr ((VAR & HV_BUF) != 0)
                 rr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rs, (hsrc[i] + cg * BK) * 4, 0, 0));
             else
                 rr[i] = *(const f32x4*)(px.res + hsrc[i] + cg * BK);
         }
     };
-    // VAR 16 / 32: weights through a buffer resource too (SGPR base + one VGPR offset
+    // HV_BUF_SC1 / HV_BUF: weights through a buffer resource too (SGPR base + one VGPR offset
     // + per-chunk SGPR/immediate offsets, instead of a 64-bit address per chunk)
     const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), (short)0,
                                                                          0x7fffffff, 0x00020000);
     const int wvo = ((n0 + sr) * BK + sc) * 4;
     auto bload = [&](f32x4 (&rb)[B_LD], int kc) {
         if (ABL & 1) return;
-        if constexpr ((VAR & 48) != 0) {
+        if constexpr ((VAR & HV_ANY_BUF) != 0) {
 #pragma unroll
             for (int i = 0; i < B_LD; ++i)
                 rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
@@ -1056,9 +1099,9 @@ __device__ __forceinline__ void halo_tile(
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
-                            // VAR bit 128 (train forward): the lo x lo term too -- products exact
+                            // HV_H3_LOLO (train forward): the lo x lo term too -- products exact
                             // to ~2^-33, smallest first
-                            if constexpr ((VAR & 128) != 0)
+                            if constexpr ((VAR & HV_H3_LOLO) != 0)
                                 at[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bl[j], at[i][j], 0, 0, 0);
                             at[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], at[i][j], 0, 0, 0);
                             at[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], at[i][j], 0, 0, 0);
@@ -1111,8 +1154,8 @@ __device__ __forceinline__ void halo_tile(
     }
 
     // the last chunk ended with a barrier: the staging buffers are free
-    halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, ABL, (VSWZ ? BN : BN + 8), (VAR & 8) != 0, XE,
-                  (VAR & 16) ? 2 : (VAR & 32) ? 1 : 0>(
+    halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, ABL, (VSWZ ? BN : BN + 8), (VAR & HV_EARLY_EPI) != 0, XE,
+                  (VAR & HV_BUF_SC1) ? 2 : (VAR & HV_BUF) ? 1 : 0>(
         acc, scale, shift, resid, out, out_rs, M, m0, n0, smem, ex, fx, H3 ? &guard : nullptr);
 }
 

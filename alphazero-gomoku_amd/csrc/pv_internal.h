@@ -31,19 +31,52 @@ struct GemmProb {
 struct GemmPair { GemmProb p[2]; int ntn0; };
 struct BlockBn { int first, second; };
 
-// kernel launchers (pv_conv.hip, pv_heads.hip, pv_pack.hip, pv_train.hip)
-hipError_t launch_conv3x3(int C, int epi, const float* in, const float* wp, const float* scale,
-                          const float* shift, const float* resid, float* out, int M, hipStream_t st);
+// kernel launchers (pv_conv.hip, pv_conv_train.hip, pv_stem.hip, pv_heads.hip, pv_pack.hip, pv_train.hip)
+// One eval 3x3 conv launch (pv_conv.hip): out = epilogue(conv(in, wp)) over M pixels.  Host
+// side only: the kernels keep their own parameter lists.
+struct ConvCall {
+    const float* in;
+    const float* wp;
+    const float* scale;
+    const float* shift;
+    const float* resid;
+    float* out;
+    int M;
+    hipStream_t st;
+};
+hipError_t launch_conv3x3(int C, int epi, const ConvCall& c);
 struct EpiX;
 struct ProX;
 struct FinX;
 constexpr int TRAIN_BM = 128;   // rows per M tile of conv3x3_train (BN partials granularity)
-// oscale (forward convs only): the split-fp16 weights of pack_h3 are passed as wp and the
-// raw output is multiplied by oscale[c] (= 2^-e of the layer, exact); nullptr: fp32 weights
-hipError_t launch_conv3x3_train(int C, int epi, int xe, const float* in, const float* wp, const float* resid,
-                                float* out, int M, const EpiX& ex, hipStream_t st, const ProX* px = nullptr,
-                                const FinX* fx = nullptr, const float* oscale = nullptr, unsigned* h3ovf = nullptr,
-                                const unsigned* dmax = nullptr);
+// One train-step conv launch (pv_conv_train.hip; EpiX / ProX / FinX: pv_halo.h).
+struct TrainConv {
+    int epi, xe;
+    const float* in;
+    const float* wp;
+    const float* resid;
+    float* out;
+    int M;
+    const EpiX* ex;
+    const ProX* px = nullptr;   // forward: the input layer's BN applied in the staging
+    const FinX* fx = nullptr;   // the BN finalize run by the last workgroup of each N tile
+    // oscale: the split-fp16 weights of pack_h3 are passed as wp and the raw output is
+    // multiplied by oscale[c] (= 2^-e of the layer, exact); nullptr: fp32 weights
+    const float* oscale = nullptr;
+    unsigned* h3ovf = nullptr;        // split-fp16 forward: where a range overflow is posted
+    const unsigned* dmax = nullptr;   // split-fp16 dgrad: the bits of the input's max |dz|
+};
+hipError_t launch_conv3x3_train(int C, const TrainConv& c, hipStream_t st);
+// Raises a kernel instantiation's dynamic-LDS limit before its first launch; `done` is the
+// launcher's static flag for that instantiation.
+template <class K>
+inline hipError_t set_dynamic_lds(K* kernel, int bytes, bool& done)
+{
+    if (done) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = e == hipSuccess;
+    return e;
+}
 // process-wide tuning variables (azg_pv_set_tuning, pv_tuning.hip: one table row per key)
 extern int g_conv_shape_override;   // pv_conv.hip
 extern int g_conv_autotune;
@@ -52,10 +85,10 @@ extern int g_conv_variant;
 extern int g_ablation_shape;
 extern int g_conv_tail_split;
 extern int g_conv_var;
-extern int g_stem_variant;
+extern int g_stem_variant;         // pv_stem.hip
 extern int g_stem_ablation;
-extern int g_tower_mode;
-extern int g_train_h3;         // the train step's forward convs in split-fp16 (2: four products, 1: three, 0: fp32)
+extern int g_tower_mode;           // pv_eval.hip
+extern int g_train_h3;         // pv_conv_train.hip: the train step's forward convs in split-fp16 (2: four products, 1: three, 0: fp32)
 extern int g_train_dgrad_h3;   // the train step's dgrad convs, likewise
 extern int g_tower_shape;      // pv_tower.hip
 extern int g_tower_ablation;
@@ -152,9 +185,7 @@ hipError_t launch_repack_all(const float* params, const int64_t* conv_offs, int 
                              const float* stem_w, float* ws, const float* wpf, const float* wv1, float* wfc,
                              const float* stats, const void* desc, int nbn, float* scale, float* shift,
                              hipStream_t st, int part = 0);
-hipError_t launch_conv3x3_h3(int shape, int C, int epi, const float* in, const float* wp, const float* scale,
-                             const float* shift, const float* resid, float* out, int M, hipStream_t st,
-                             unsigned* ring, unsigned seq);
+hipError_t launch_conv3x3_h3(int shape, int C, int epi, const ConvCall& c, unsigned* ring, unsigned seq);
 hipError_t launch_pack_h3(const float* params, const int64_t* offs, int nl, int C, const int* conv_bn_off,
                           const float* scale, int* exps, void* wp16, float* scale16, float* inv, hipStream_t st);
 hipError_t launch_pack_h3_dgrad(const float* params, const int64_t* offs, int nl, int C, const int* exps, void* wd16,

@@ -17,10 +17,10 @@
 // workgroup barrier; one lane adds the tile count to the (layer, M tile) counter
 // with an agent-scope atomic.  Consumer: one lane polls the (up to) three counters
 // with relaxed agent-scope loads (global_load sc1) until each is complete, then
-//  * VAR bit 16 clear (64x64 / 128x64 tiles, 2-4 workgroups per CU): ONE agent-scope
+//  * HV_BUF_SC1 clear (64x64 / 128x64 tiles, 2-4 workgroups per CU): ONE agent-scope
 //    acquire, s_waitcnt vmcnt(0), workgroup barrier, plain loads -- the form valid at
 //    any occupancy;
-//  * VAR bit 16 set (the 16-wave 128x128 tile, exactly ONE workgroup per CU, checked
+//  * HV_BUF_SC1 set (the 16-wave 128x128 tile, exactly ONE workgroup per CU, checked
 //    at launch): s_waitcnt vmcnt(0), workgroup barrier, and EVERY load of handed-off
 //    bytes (halo rows, the epilogue's residual) is a 16-B sc1 buffer load -- row 1 of
 //    the guide's measured hand-off table, which requires one workgroup per CU in
@@ -86,14 +86,14 @@ constexpr int tower_min_waves() { return NW_ >= 16 ? 4 : BN_ >= 128 ? 2 : 4; }
 // dynamic LDS of a tower launch: the 16-wave tile asks for more than half of the CU's
 // 160 KiB so that one workgroup per CU is guaranteed by LDS alone (the sc1-load
 // hand-off is valid only there), whatever the register allocation
-// VAR bit 256: the tile body is h3_tile (pv_h3.h: split-fp16, LDS-DMA weight stages of one
+// HV_H3_TILE: the tile body is h3_tile (pv_h3.h: split-fp16, LDS-DMA weight stages of one
 // tap, three stage buffers), else halo_tile
 constexpr int kH3TileTps = 1, kH3TileNwb = 3;
 template <int C, int BN, int WM, int TM, int NW, int VAR>
 constexpr int tower_body_lds()
 {
-    if constexpr ((VAR & 256) != 0) return H3Tile<C, BN, WM, TM, NW, kH3TileTps, kH3TileNwb>::LDS;
-    else return halo_lds_bytes<C, BN, WM, TM, NW, VAR & 255>();
+    if constexpr ((VAR & HV_H3_TILE) != 0) return H3Tile<C, BN, WM, TM, NW, kH3TileTps, kH3TileNwb>::LDS;
+    else return halo_lds_bytes<C, BN, WM, TM, NW, VAR & ~HV_H3_TILE>();
 }
 template <int C, int BN, int WM, int TM, int NW, int VAR>
 constexpr int tower_lds_bytes()
@@ -217,7 +217,8 @@ template <int C, int BN_, int WM_, int TM_, int NW_, int VAR = 0, int HABL = 0>
 __global__ __launch_bounds__(64 * NW_, (tower_min_waves<BN_, NW_>())) void conv_tower(const TowerArgs a)
 {
     using T = ConvTile<C, BN_, WM_, TM_, NW_>;
-    static_assert(!((VAR & 48) && (VAR & 12)), "buffer halo / residual loads (VAR 16, 32) exclude LDS-DMA (4) and early epilogue loads (8)");
+    static_assert(!((VAR & HV_ANY_BUF) && (VAR & (HV_LDS_DMA | HV_EARLY_EPI))),
+                  "buffer halo / residual loads (HV_BUF_SC1, HV_BUF) exclude HV_LDS_DMA and HV_EARLY_EPI");
     constexpr int NTN = C / T::BN;
     constexpr int LDS_FLOATS = tower_body_lds<C, BN_, WM_, TM_, NW_, VAR>() / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -259,9 +260,9 @@ __global__ __launch_bounds__(64 * NW_, (tower_min_waves<BN_, NW_>())) void conv_
                     }
                     if (waited > 10000u || t1 - t0 > 10000u) tower_wait_stats(a.diag, waited, (unsigned)(t1 - t0));
                 }
-                // VAR bit 16 (one workgroup per CU): every dependent read is an sc1 load,
+                // HV_BUF_SC1 (one workgroup per CU): every dependent read is an sc1 load,
                 // no acquire; otherwise ONE agent-scope acquire (L1 invalidate) here
-                if constexpr ((VAR & 16) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                if constexpr ((VAR & HV_BUF_SC1) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             // what this tile's workgroup publishes about itself (read only by a timed-out
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(64 * NW_, (tower_min_waves<BN_, NW_>())) void conv_
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(Ly.out, (short)0, a.act_bytes, 0x00020000);
         for (int nt = nt0; nt < nt0 + grp; ++nt) {
             if (nt > nt0) __syncthreads();        // the previous tile's epilogue is done with LDS
-            if constexpr ((VAR & 256) != 0)
+            if constexpr ((VAR & HV_H3_TILE) != 0)
                 h3_tile<C, BN_, WM_, TM_, NW_, kH3TileTps, kH3TileNwb, EPI_BN_OPTRES_RELU, true, 1>(
                     Ly.in, Ly.wp, Ly.scale, Ly.shift, Ly.resid, Ly.out, rs, a.M, mt * T::BM, nt * T::BN, smem,
                     H3Guard{a.ring_ovf, a.seq});
@@ -313,13 +314,13 @@ static hipError_t launch_tower_t(const TowerArgs& a, hipStream_t st, int* grid_o
         if (e != hipSuccess) return e;
         if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
         if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        // the sc1-load hand-off (VAR 16) is valid at one workgroup per CU only: the
+        // the sc1-load hand-off (HV_BUF_SC1) is valid at one workgroup per CU only: the
         // product refuses to launch it at any other residency (the study build runs the
         // round-2 two-per-CU form on purpose, key 31)
 #ifndef AZG_AB_STUDIES
-        if ((VAR & 16) && per_cu != 1) return hipErrorInvalidConfiguration;
+        if ((VAR & HV_BUF_SC1) && per_cu != 1) return hipErrorInvalidConfiguration;
 #else
-        if ((VAR & 16) && NW >= 16 && per_cu != 1) return hipErrorInvalidConfiguration;
+        if ((VAR & HV_BUF_SC1) && NW >= 16 && per_cu != 1) return hipErrorInvalidConfiguration;
 #endif
         grid = max(1, per_cu) * cus;
     }
@@ -329,7 +330,7 @@ static hipError_t launch_tower_t(const TowerArgs& a, hipStream_t st, int* grid_o
 }
 
 int g_tower_ablation = 0;
-int g_tower_var = 0;     // halo_tile VAR of the 128x64 C=128 tower (0 = product; 1..8, 12 A/B studies)
+int g_tower_var = 0;     // study body of the 128x64 C=128 tower (0 = product; 1..8, 12: that HaloVar mask; 13-16 below)
 int g_tower_shape = 8;   // forced shape when g_tower_mode == 1: 5 = 64x64 (4 waves), 8 = 128x64 (8 waves),
                          // 10 = 128x128 (16 waves, one workgroup per CU; C = 128)
 
@@ -350,9 +351,9 @@ size_t tower_prod_bytes(int nlayers, int M)
 // H -> Y (BN, + X, ReLU), X <-> Y.  `act` are the three padded NHWC buffers
 // (act[0] holds the stem output; the result ends in act[0] or act[2], returned in
 // *result).  `sync` must hold tower_sync_bytes(2*NB, M) bytes.
-int g_h3_tower_var = 1;   // key 20: the H3 tower body, 1 = board-keyed halo swizzle (VAR 99, default), 0 = row-keyed (98)
+int g_h3_tower_var = 1;   // key 20: the H3 tower body, 1 = board-keyed halo swizzle (kHaloH3Eval, default), 0 = row-keyed (kHaloH3EvalRowKeyed)
 // key 19: split-fp16 (H3) eval residual convs: 2 (default) the 16x16x32 board tower at C = 128
-// (pv_board16.hip; C = 256 as 1), 1 the 32x32x16 forms (pv_halo.h VAR bit 64), 0 fp32 MFMA
+// (pv_board16.hip; C = 256 as 1), 1 the 32x32x16 forms (pv_halo.h HV_H3), 0 fp32 MFMA
 int g_tower_h3 = 2;
 
 hipError_t launch_tower(int C, int NB, int shape, float* const act[3], const float* wpack, const float* scale,
@@ -399,29 +400,28 @@ hipError_t launch_tower(int C, int NB, int shape, float* const act[3], const flo
     hipError_t e = hipMemsetAsync(sync, 0, tower_sync_bytes(2 * NB, M), st);
     if (e != hipSuccess) return e;
     if (h3) {   // wpack / scale are the split-fp16 packs (pv_pack.hip pack_h3)
-        // VAR 99 = H3 + buffer addressing + weights staged two chunks ahead (bit 2) + the
-        // board-keyed halo swizzle (bit 1): with the fragment addresses built per tap (no
-        // spills) 3.8-4.8 % faster than the row-keyed VAR 98, whose fragment reads conflict
-        // at board-row ends (32 % of its LDS cycles; scripts/h3_tune_study.py,
-        // profiles/r5_h3_study.md); bitwise equal to every other form.  Key 20 = 0: VAR 98.
+        // kHaloH3Eval (pv_halo.h): with the fragment addresses built per tap (no spills)
+        // 3.8-4.8 % faster than the row-keyed form, whose fragment reads conflict at
+        // board-row ends (32 % of its LDS cycles; scripts/h3_tune_study.py,
+        // profiles/r5_h3_study.md); bitwise equal to every other form.  Key 20 = 0: row-keyed.
         const bool vs = g_h3_tower_var == 1;
-        // shape 12: h3_tile 128x128, 4 waves of 64x64 (VAR 355 = 99 | 256), bitwise equal
+        // shape 12: h3_tile 128x128, 4 waves of 64x64, bitwise equal
         if (shape == 12) {
-            if (C == 128) return launch_tower_t<128, 128, 2, 2, 4, 355>(a, st, nullptr);
-            if (C == 256) return launch_tower_t<256, 128, 2, 2, 4, 355>(a, st, nullptr);
+            if (C == 128) return launch_tower_t<128, 128, 2, 2, 4, kHaloH3TileTower>(a, st, nullptr);
+            if (C == 256) return launch_tower_t<256, 128, 2, 2, 4, kHaloH3TileTower>(a, st, nullptr);
             return hipErrorInvalidValue;
         }
         switch (C) {
             case 128:
-                if (shape == 5) return vs ? launch_tower_t<128, 64, 2, 1, 4, 99>(a, st, nullptr)
-                                          : launch_tower_t<128, 64, 2, 1, 4, 98>(a, st, nullptr);
-                return vs ? launch_tower_t<128, 64, 4, 1, 8, 99>(a, st, nullptr)
-                          : launch_tower_t<128, 64, 4, 1, 8, 98>(a, st, nullptr);
+                if (shape == 5) return vs ? launch_tower_t<128, 64, 2, 1, 4, kHaloH3Eval>(a, st, nullptr)
+                                          : launch_tower_t<128, 64, 2, 1, 4, kHaloH3EvalRowKeyed>(a, st, nullptr);
+                return vs ? launch_tower_t<128, 64, 4, 1, 8, kHaloH3Eval>(a, st, nullptr)
+                          : launch_tower_t<128, 64, 4, 1, 8, kHaloH3EvalRowKeyed>(a, st, nullptr);
             case 256:
-                if (shape == 5) return vs ? launch_tower_t<256, 64, 2, 1, 4, 99>(a, st, nullptr)
-                                          : launch_tower_t<256, 64, 2, 1, 4, 98>(a, st, nullptr);
-                return vs ? launch_tower_t<256, 64, 4, 1, 8, 99>(a, st, nullptr)
-                          : launch_tower_t<256, 64, 4, 1, 8, 98>(a, st, nullptr);
+                if (shape == 5) return vs ? launch_tower_t<256, 64, 2, 1, 4, kHaloH3Eval>(a, st, nullptr)
+                                          : launch_tower_t<256, 64, 2, 1, 4, kHaloH3EvalRowKeyed>(a, st, nullptr);
+                return vs ? launch_tower_t<256, 64, 4, 1, 8, kHaloH3Eval>(a, st, nullptr)
+                          : launch_tower_t<256, 64, 4, 1, 8, kHaloH3EvalRowKeyed>(a, st, nullptr);
             default: return hipErrorInvalidValue;
         }
     }
@@ -429,67 +429,67 @@ hipError_t launch_tower(int C, int NB, int shape, float* const act[3], const flo
     // traffic ablations of the 128x64 tower (key 8 bits 4 / 8: no weight / no halo loads)
     if (shape == 8 && (a.abl & 12)) {
         const bool nw = a.abl & 4, nh = a.abl & 8;
-        if (C == 256 && nw && nh) return launch_tower_t<256, 64, 4, 1, 8, 32, 3>(a, st, nullptr);
-        if (C == 256 && nw) return launch_tower_t<256, 64, 4, 1, 8, 32, 1>(a, st, nullptr);
-        if (C == 256 && nh) return launch_tower_t<256, 64, 4, 1, 8, 32, 2>(a, st, nullptr);
-        if (C == 128 && nw && nh) return launch_tower_t<128, 64, 4, 1, 8, 32, 3>(a, st, nullptr);
-        if (C == 128 && nw) return launch_tower_t<128, 64, 4, 1, 8, 32, 1>(a, st, nullptr);
-        if (C == 128 && nh) return launch_tower_t<128, 64, 4, 1, 8, 32, 2>(a, st, nullptr);
+        if (C == 256 && nw && nh) return launch_tower_t<256, 64, 4, 1, 8, HV_BUF, 3>(a, st, nullptr);
+        if (C == 256 && nw) return launch_tower_t<256, 64, 4, 1, 8, HV_BUF, 1>(a, st, nullptr);
+        if (C == 256 && nh) return launch_tower_t<256, 64, 4, 1, 8, HV_BUF, 2>(a, st, nullptr);
+        if (C == 128 && nw && nh) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF, 3>(a, st, nullptr);
+        if (C == 128 && nw) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF, 1>(a, st, nullptr);
+        if (C == 128 && nh) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF, 2>(a, st, nullptr);
     }
     if (g_tower_coh && (shape == 8 || shape == 5)) {   // study only: sc1 loads at 2-4 workgroups per CU
-        if (C == 128 && shape == 8) return launch_tower_t<128, 64, 4, 1, 8, 16>(a, st, nullptr);
-        if (C == 128) return launch_tower_t<128, 64, 2, 1, 4, 16>(a, st, nullptr);
+        if (C == 128 && shape == 8) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF_SC1>(a, st, nullptr);
+        if (C == 128) return launch_tower_t<128, 64, 2, 1, 4, HV_BUF_SC1>(a, st, nullptr);
     }
     if (C == 128 && shape == 9) {   // 128x128 tiles, 2 accumulators per wave, LDS-DMA staging (A/B study)
-        if (g_tower_var == 5) return launch_tower_t<128, 128, 4, 1, 8, 5>(a, st, nullptr);
-        return launch_tower_t<128, 128, 4, 1, 8, 4>(a, st, nullptr);
+        if (g_tower_var == 5) return launch_tower_t<128, 128, 4, 1, 8, HV_LDS_DMA | HV_BOARD_SWZ>(a, st, nullptr);
+        return launch_tower_t<128, 128, 4, 1, 8, HV_LDS_DMA>(a, st, nullptr);
     }
     if (C == 128 && shape == 8 && g_tower_var != 0) {   // A/B variants (bitwise identical)
-        if (g_tower_var == 3) return launch_tower_t<128, 64, 4, 1, 8, 3>(a, st, nullptr);
-        if (g_tower_var == 1) return launch_tower_t<128, 64, 4, 1, 8, 1>(a, st, nullptr);
-        if (g_tower_var == 2) return launch_tower_t<128, 64, 4, 1, 8, 2>(a, st, nullptr);
-        if (g_tower_var == 4) return launch_tower_t<128, 64, 4, 1, 8, 4>(a, st, nullptr);
-        if (g_tower_var == 5) return launch_tower_t<128, 64, 4, 1, 8, 5>(a, st, nullptr);
-        if (g_tower_var == 8) return launch_tower_t<128, 64, 4, 1, 8, 8>(a, st, nullptr);
-        if (g_tower_var == 6) return launch_tower_t<128, 64, 4, 1, 8, 6>(a, st, nullptr);
-        if (g_tower_var == 7) return launch_tower_t<128, 64, 4, 1, 8, 7>(a, st, nullptr);
-        if (g_tower_var == 12) return launch_tower_t<128, 64, 4, 1, 8, 12>(a, st, nullptr);
-        if (g_tower_var == 14) return launch_tower_t<128, 64, 4, 1, 8, 33>(a, st, nullptr);
-        if (g_tower_var == 15) return launch_tower_t<128, 64, 4, 1, 8, 34>(a, st, nullptr);
+        if (g_tower_var == 3) return launch_tower_t<128, 64, 4, 1, 8, HV_W_AHEAD2 | HV_BOARD_SWZ>(a, st, nullptr);
+        if (g_tower_var == 1) return launch_tower_t<128, 64, 4, 1, 8, HV_BOARD_SWZ>(a, st, nullptr);
+        if (g_tower_var == 2) return launch_tower_t<128, 64, 4, 1, 8, HV_W_AHEAD2>(a, st, nullptr);
+        if (g_tower_var == 4) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA>(a, st, nullptr);
+        if (g_tower_var == 5) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA | HV_BOARD_SWZ>(a, st, nullptr);
+        if (g_tower_var == 8) return launch_tower_t<128, 64, 4, 1, 8, HV_EARLY_EPI>(a, st, nullptr);
+        if (g_tower_var == 6) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA | HV_W_AHEAD2>(a, st, nullptr);
+        if (g_tower_var == 7) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA | HV_W_AHEAD2 | HV_BOARD_SWZ>(a, st, nullptr);
+        if (g_tower_var == 12) return launch_tower_t<128, 64, 4, 1, 8, HV_EARLY_EPI | HV_LDS_DMA>(a, st, nullptr);
+        if (g_tower_var == 14) return launch_tower_t<128, 64, 4, 1, 8, kHaloTower256>(a, st, nullptr);
+        if (g_tower_var == 15) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF | HV_W_AHEAD2>(a, st, nullptr);
     }
-    if (C == 256 && shape == 8 && g_tower_var == 2)   // weights staged two chunks ahead (VAR bit 2), C = 256
-        return launch_tower_t<256, 64, 4, 1, 8, 34>(a, st, nullptr);
-    if (C == 256 && shape == 8 && g_tower_var == 16)   // round-3 product body at C = 256 (VAR 32)
-        return launch_tower_t<256, 64, 4, 1, 8, 32>(a, st, nullptr);
-    if (C == 256 && shape == 5 && g_tower_var == 16)   // round-3 64x64 body at C = 256 (VAR 32)
-        return launch_tower_t<256, 64, 2, 1, 4, 32>(a, st, nullptr);
+    if (C == 256 && shape == 8 && g_tower_var == 2)   // weights staged two chunks ahead, C = 256
+        return launch_tower_t<256, 64, 4, 1, 8, HV_BUF | HV_W_AHEAD2>(a, st, nullptr);
+    if (C == 256 && shape == 8 && g_tower_var == 16)   // round-3 product body at C = 256
+        return launch_tower_t<256, 64, 4, 1, 8, HV_BUF>(a, st, nullptr);
+    if (C == 256 && shape == 5 && g_tower_var == 16)   // round-3 64x64 body at C = 256
+        return launch_tower_t<256, 64, 2, 1, 4, HV_BUF>(a, st, nullptr);
     if (C == 256 && shape == 10) {   // 16-wave 128x128 tile at C = 256 (spills; traffic study)
-        if (g_tower_var == 1) return launch_tower_t<256, 128, 4, 1, 16, 32>(a, st, nullptr);
-        return launch_tower_t<256, 128, 4, 1, 16, 16>(a, st, nullptr);
+        if (g_tower_var == 1) return launch_tower_t<256, 128, 4, 1, 16, HV_BUF>(a, st, nullptr);
+        return launch_tower_t<256, 128, 4, 1, 16, HV_BUF_SC1>(a, st, nullptr);
     }
-    if (C == 128 && shape == 5 && g_tower_var == 14) return launch_tower_t<128, 64, 2, 1, 4, 33>(a, st, nullptr);
+    if (C == 128 && shape == 5 && g_tower_var == 14) return launch_tower_t<128, 64, 2, 1, 4, kHaloTower256>(a, st, nullptr);
     if (C == 128 && shape == 10 && g_tower_var == 1)   // 16-wave tile with the acquire instead of sc1 loads
-        return launch_tower_t<128, 128, 4, 1, 16, 32>(a, st, nullptr);
-    if (C == 128 && shape == 8 && g_tower_var == 13)   // round-2 acquire form: 64-bit pointer loads (VAR 0)
+        return launch_tower_t<128, 128, 4, 1, 16, HV_BUF>(a, st, nullptr);
+    if (C == 128 && shape == 8 && g_tower_var == 13)   // round-2 acquire form: 64-bit pointer loads (no HaloVar bit)
         return launch_tower_t<128, 64, 4, 1, 8, 0>(a, st, nullptr);
 #endif
     switch (C) {
         case 64:
-            if (shape == 8) return launch_tower_t<64, 64, 4, 1, 8, 32>(a, st, nullptr);
-            return launch_tower_t<64, 64, 2, 1, 4, 32>(a, st, nullptr);
+            if (shape == 8) return launch_tower_t<64, 64, 4, 1, 8, HV_BUF>(a, st, nullptr);
+            return launch_tower_t<64, 64, 2, 1, 4, HV_BUF>(a, st, nullptr);
         case 128:
-            if (shape == 10) return launch_tower_t<128, 128, 4, 1, 16, 16>(a, st, nullptr);
-            if (shape == 8) return launch_tower_t<128, 64, 4, 1, 8, 32>(a, st, nullptr);
-            return launch_tower_t<128, 64, 2, 1, 4, 32>(a, st, nullptr);
+            if (shape == 10) return launch_tower_t<128, 128, 4, 1, 16, HV_BUF_SC1>(a, st, nullptr);
+            if (shape == 8) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF>(a, st, nullptr);
+            return launch_tower_t<128, 64, 2, 1, 4, HV_BUF>(a, st, nullptr);
         case 256:
-            // C = 256: halo rows keyed on the board position (VAR bit 1: conflict-free
+            // C = 256: halo rows keyed on the board position (HV_BOARD_SWZ: conflict-free
             // fragment reads, unpadded epilogue tile), bitwise equal, scripts/gpu_r4o.sh:
             // 128x64 tile 90.0 vs 86.4 % of peak at B = 512, equal at 128 / 300 / 1024 /
             // 2048; 64x64 tile 79.4 vs 77.4 % at B = 300, 89.5 vs 88.2 % at 512, 55.4 vs
             // 56.4 % at 128.  At C = 128 the same body is slower (89.5 vs 91.2 % at B =
-            // 3456), so C = 128 keeps VAR 32.
-            if (shape == 8) return launch_tower_t<256, 64, 4, 1, 8, 33>(a, st, nullptr);
-            return launch_tower_t<256, 64, 2, 1, 4, 33>(a, st, nullptr);
+            // 3456), so C = 128 keeps HV_BUF alone.
+            if (shape == 8) return launch_tower_t<256, 64, 4, 1, 8, kHaloTower256>(a, st, nullptr);
+            return launch_tower_t<256, 64, 2, 1, 4, kHaloTower256>(a, st, nullptr);
         default: return hipErrorInvalidValue;
     }
 }

@@ -858,9 +858,15 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
             fx = fin_args(fin, xe == XE_STATS);
             fx.cnt = w->fincnt;
         }
-        AZG_CK(launch_conv3x3_train(C, epi, xe, in, wp, res, out, M, ex, st, nullptr, fin >= 0 ? &fx : nullptr, osc,
-                                    osc && !dmx ? h->posted.train_ovf_dev : nullptr, dmx),
-               "train: conv3x3");
+        TrainConv t{};
+        t.epi = epi, t.xe = xe;
+        t.in = in, t.wp = wp, t.resid = res, t.out = out, t.M = M;
+        t.ex = &ex;
+        t.fx = fin >= 0 ? &fx : nullptr;
+        t.oscale = osc;
+        t.h3ovf = osc && !dmx ? h->posted.train_ovf_dev : nullptr;
+        t.dmax = dmx;
+        AZG_CK(launch_conv3x3_train(C, t, st), "train: conv3x3");
         prof_end(h, pr, st);
         return 0;
     };
@@ -932,9 +938,15 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
             const ProX px{p.res, w->bscale + o, w->bshift + o, p.out};
             FinX fx = fin_args(fin, true);
             fx.cnt = w->fincnt;
-            AZG_CK(launch_conv3x3_train(C, EPI_RAW, XE_STATS, p.z, fwd_w(ci), nullptr, out, M, ex, st, &px,
-                                        ffin ? &fx : nullptr, fwd_s(ci), fh3 ? h->posted.train_ovf_dev : nullptr),
-                   "train: conv3x3 (fused BN apply)");
+            TrainConv t{};
+            t.epi = EPI_RAW, t.xe = XE_STATS;
+            t.in = p.z, t.wp = fwd_w(ci), t.resid = nullptr, t.out = out, t.M = M;
+            t.ex = &ex;
+            t.px = &px;
+            t.fx = ffin ? &fx : nullptr;
+            t.oscale = fwd_s(ci);
+            t.h3ovf = fh3 ? h->posted.train_ovf_dev : nullptr;
+            AZG_CK(launch_conv3x3_train(C, t, st), "train: conv3x3 (fused BN apply)");
             prof_end(h, pr, st);
             if (!ffin) return fin_fwd(fin, TRAIN_BM, ntt);
             return 0;

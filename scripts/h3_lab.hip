@@ -1,6 +1,6 @@
 // Split-fp16 (H3) residual-conv tile lab (round 5).
 //
-// Stand-alone executable: times per-layer launches of halo_tile (pv_halo.h, VAR bit 64)
+// Stand-alone executable: times per-layer launches of halo_tile (pv_halo.h, HV_H3)
 // at several tile shapes / register blockings on synthetic operands (padded NHWC
 // activations with a zero halo, split fp16 weights in the pack_h3 layout), reports
 // device time per launch (hipEvents), fp32-equivalent TFLOP/s, and whether every
@@ -41,9 +41,7 @@ __global__ __launch_bounds__(64 * NW_, WPE) void lab_conv(const float* __restric
     using T = ConvTile<C, BN_, WM_, TM_, NW_>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NTN = C / T::BN;
-    const int L = blockIdx.x, nt = gridDim.x;
-    const int xcd = L & 7, q8 = nt >> 3, r8 = nt & 7;
-    const int t = xcd * q8 + min(xcd, r8) + (L >> 3);
+    const int t = xcd_tile(blockIdx.x, gridDim.x);
     halo_tile<C, BN_, WM_, TM_, NW_, EPI_BN_RES_RELU, false, 0, VAR>(
         in, wp, scale, shift, resid, out, __builtin_amdgcn_make_buffer_rsrc(out, (short)0, 0, 0x00020000), M,
         (t / NTN) * T::BM, (t % NTN) * T::BN, smem, EpiX{}, ProX{}, FinX{}, guard);
@@ -59,9 +57,7 @@ __global__ __launch_bounds__(64 * NW_, WPE) void lab_h3(const float* __restrict_
     using T = ConvTile<C, BN_, WM_, TM_, NW_>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NTN = C / T::BN;
-    const int L = blockIdx.x, nt = gridDim.x;
-    const int xcd = L & 7, q8 = nt >> 3, r8 = nt & 7;
-    const int t = xcd * q8 + min(xcd, r8) + (L >> 3);
+    const int t = xcd_tile(blockIdx.x, gridDim.x);
     h3_tile<C, BN_, WM_, TM_, NW_, TPS, NWB, EPI_BN_RES_RELU, false, 0, ABL & 7, ABL & ~7>(
         in, wp, scale, shift, resid, out, __builtin_amdgcn_make_buffer_rsrc(out, (short)0, 0, 0x00020000), M,
         (t / NTN) * T::BM, (t % NTN) * T::BN, smem, guard);
@@ -80,9 +76,7 @@ __global__ __launch_bounds__(256, 2) void lab_h3_16(const float* __restrict__ in
                   HR = H::HR, NST = 9, NSTAGE = CG * 9, PPW = H::PPW, BNP = BN / 8, NWB = 3;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NTN = C / BN;
-    const int L = blockIdx.x, nt = gridDim.x;
-    const int xcd = L & 7, q8 = nt >> 3, r8 = nt & 7;
-    const int t = xcd * q8 + min(xcd, r8) + (L >> 3);
+    const int t = xcd_tile(blockIdx.x, gridDim.x);
     const int m0 = (t / NTN) * BM, n0 = (t % NTN) * BN;
     float* Ah = smem;
     float* Bs = smem + HR * BK;
@@ -308,10 +302,10 @@ template <int C>
 static std::vector<Variant> variants()
 {
     return {
-        V(C, 64, 4, 1, 8, 99, 2),    // product per-layer form: 128x64, 8 waves, wave 32x32
+        V(C, 64, 4, 1, 8, kHaloH3Eval, 2),    // product per-layer form: 128x64, 8 waves, wave 32x32
         Variant{"h3_tile 128x128 nw4 16x16x32 (not bitwise)", C, 128, 128,
                 (size_t)H3Tile<C, 128, 2, 2, 4, 1, 3>::LDS, launch_16<C>, prep_16<C>},
-        V(C, 128, 2, 2, 4, 99, 2),   // 128x128, 4 waves as 2x2, wave 64x64
+        V(C, 128, 2, 2, 4, kHaloH3Eval, 2),   // 128x128, 4 waves as 2x2, wave 64x64
         // h3_tile (pv_h3.h): LDS-DMA weight stages, counted waits, raw barriers
         VH(C, 64, 4, 1, 8, 1, 2, 4),     // 128x64, wave 32x32, 1-tap stages
         VH(C, 64, 4, 1, 8, 1, 3, 4),     // ... three stage buffers
