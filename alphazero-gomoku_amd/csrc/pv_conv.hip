@@ -1,26 +1,16 @@
-// 3x3 convolution (pad 1, no bias) as an fp32-MFMA implicit GEMM for gfx950,
-// with the BatchNorm / residual / ReLU epilogue fused.
+// Per-layer 3x3 convolution (pad 1, no bias) of the eval forward: the halo-staged
+// fp32-MFMA / split-fp16 tile of pv_halo.h (halo_tile), one launch per conv, with the
+// BatchNorm / residual / ReLU epilogue fused.
 //
 // Replaces the ATen conv2d + batch_norm + relu (+ in-place residual add) chain of
-// the reference ResidualBlock (network.py:9-26) in the eval forward, one launch per
-// conv.  The stem is pv_stem.hip, the train step's conv pv_conv_train.hip.
+// the reference ResidualBlock (network.py:9-26).  The stem is pv_stem.hip, the
+// persistent tower pv_tower.hip, the train step's conv pv_conv_train.hip.
 //
-// GEMM view: rows m = pixel of the batch (B*225), cols n = output channel,
-// K = 9 taps x C input channels.  A[m][k] is read straight from the padded NHWC
-// activation (the halo makes every tap an unconditional 16-byte load), B is the
-// weight re-packed to [kchunk][n][32] so a K-chunk of 32 is one contiguous block.
-//
-// Tile: BM pixels x BN channels per 256-thread workgroup (shape picked per
-// launch, see pick_conv_tile), K-chunk 32.  4 waves, each owning TM x TN 32x32
-// accumulators of v_mfma_f32_32x32x2_f32 (exact f32 FMA chain: the parity budget
-// is 1e-5 fp32, so no bf16/xf32).  LDS holds two chunks (double buffer) of
-// unpadded 128-B rows whose 16-B chunks are XOR-swizzled by row, so every
-// ds_read_b128 fragment load is bank-conflict free.  Global->LDS staging is
-// register staged and issued before the MFMAs of the current chunk
-// (async-STAGE split), one barrier per chunk.
-//
-// Lane l of an MFMA step s uses K index h*16+s (h = l>>5) for both A and B, so
-// each lane's 16 A values and 16 B values of a chunk are contiguous in LDS.
+// This file is the kernel wrapper (conv3x3_halo: one BM x BN tile per workgroup, in
+// the XCD-aware tile order) and the host side: the tile shapes, the autotuner that
+// times them on the real operands, the tail split of the 128x64 launch and key 22's
+// tile-body variants.  Every shape and body computes the same per-element K order, so
+// none of these choices changes a result bit.
 #include "pv_internal.h"
 #include "pv_halo.h"
 
@@ -30,172 +20,8 @@
 
 namespace azg {
 
-// ABL (ablation, timing studies only; 0 in every product launch): bit 1 skips the
-// global loads, bit 2 replaces LDS fragment reads by register values, bit 4 drops
-// the per-chunk barrier, bit 8 skips the epilogue stores (kept live by a never-true
-// compare).  Results are garbage when ABL != 0.
-template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, int ABL = 0, int SB = 0>
-__global__ __launch_bounds__(64 * NW_, NW_ / 2) void conv3x3_mfma(
-    const float* __restrict__ in, const float* __restrict__ wp,
-    const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ resid, float* __restrict__ out, int M)
-{
-    using T = ConvTile<C, BN_, WM_, TM_, NW_, SB>;
-    constexpr int RPP = T::RPP;
-    constexpr int BM = T::BM, BN = T::BN, BK = T::BK, LDK = T::LDK;
-    constexpr int CG = T::CG, NCH = T::NCH, WN = T::WN, TM = T::TM, TN = T::TN;
-    constexpr int A_LD = T::A_LD, B_LD = T::B_LD;
-
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                    // [2][BM][LDK]
-    float* Bs = smem + (SB ? 1 : 2) * BM * LDK;   // [2 or 1][BN][LDK]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-    constexpr int NTN = C / BN;
-    const int t = xcd_tile(blockIdx.x, gridDim.x);   // XCD-aware tile order (pv_halo.h)
-    const int m0 = (t / NTN) * BM;
-    const int n0 = (t % NTN) * BN;
-
-    // staging: thread -> (row sr + RPP i, floats sc..sc+3)
-    const int sr = tid >> 3, sc = (tid & 7) * 4;
-    int abase[A_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-        int m = m0 + sr + RPP * i;
-        m = m < M ? m : M - 1;           // tail rows: clamp to a valid pixel, never stored
-        abase[i] = pad_off(m, C) + sc;
-    }
-    const float* wsrc = wp + (size_t)(n0 + sr) * BK + sc;
-
-    f32x4 ra[A_LD], rb[B_LD];
-    auto gload = [&](int kc) {
-        if (ABL & 1) return;
-        const int tap = kc / CG, cg = kc - tap * CG;
-        const int ky = tap / 3, kx = tap - ky * 3;
-        const int toff = ((ky - 1) * PADW + (kx - 1)) * C + cg * BK;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i) ra[i] = *(const f32x4*)(in + abase[i] + toff);
-        const float* wk = wsrc + (size_t)kc * C * BK;
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) rb[i] = *(const f32x4*)(wk + RPP * i * BK);
-    };
-    // 16-B chunk c of LDS row r is stored at chunk c ^ ((r >> 1) & 7): the 16 rows a
-    // ds_read_b128 lane group touches land on 16 distinct 4-bank slots.
-    const int wchunk = ((tid & 7) ^ ((sr >> 1) & 7)) * 4;
-    auto lstore = [&](int buf) {
-        float* a = As + buf * BM * LDK;
-        float* b = Bs + buf * BN * LDK;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i) *(f32x4*)(a + (sr + RPP * i) * LDK + wchunk) = ra[i];
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) *(f32x4*)(b + (sr + RPP * i) * LDK + wchunk) = rb[i];
-    };
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int r32 = lane & 31, h = lane >> 5;
-    const int swz = (r32 >> 1) & 7;
-    const int arow = (wm * TM * 32 + r32) * LDK;
-    const int brow = (wn * TN * 32 + r32) * LDK;
-
-    gload(0);
-    lstore(0);
-    __syncthreads();
-
-    // Two-level K sum for accuracy: each tap's C-long chain accumulates into `at`
-    // (one MFMA chain of C/2 steps), which is then added into `acc`: the rounding
-    // error grows like chain(C) + 9 instead of chain(9*C) (fp32 parity budget).
-    for (int tap = 0; tap < 9; ++tap) {
-        f32x16 at[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) at[i][j][r] = 0.f;
-#pragma unroll
-        for (int cg = 0; cg < CG; ++cg) {
-            const int kc = tap * CG + cg;
-            const int cur = SB ? 0 : (kc & 1);
-            if (kc + 1 < NCH) gload(kc + 1);
-            // keep the next chunk's global loads at the top of the chunk: without this
-            // fence hipcc sinks them to just before their vmcnt wait (latency exposed)
-            __builtin_amdgcn_sched_barrier(0);
-            const float* Ab = As + cur * BM * LDK;
-            const float* Bb = Bs + cur * BN * LDK;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 a[TM], b[TN];
-                const int rc = ((h * 4 + q) ^ swz) * 4;
-                if (ABL & 2) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) a[i] = f32x4{(float)kc, (float)q, (float)i, 1.f};
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) b[j] = f32x4{(float)q, (float)kc, 1.f, (float)j};
-                } else {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) a[i] = *(const f32x4*)(Ab + arow + i * 32 * LDK + rc);
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) b[j] = *(const f32x4*)(Bb + brow + j * 32 * LDK + rc);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            at[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][s], b[j][s], at[i][j], 0, 0, 0);
-            }
-            if (kc + 1 < NCH) {
-                if (SB) __syncthreads();   // every wave is done reading the buffer
-                lstore(SB ? 0 : cur ^ 1);
-            }
-            if (!(ABL & 4)) __syncthreads();
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] += at[i][j];
-    }
-
-    // epilogue: C/D map of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * TN * 32 + j * 32 + r32;
-        float s_ = 1.f, t_ = 0.f;
-        if (EPI == EPI_BN_RELU || EPI == EPI_BN_RES_RELU) { s_ = scale[col]; t_ = shift[col]; }
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m < M && (!(ABL & 8) || acc[i][j][r] == 1234.5f)) {
-                    const int o = pad_off(m, C) + col;
-                    float v = acc[i][j][r];
-                    if (EPI == EPI_BN_RELU) {
-                        v = fmaxf(v * s_ + t_, 0.f);
-                    } else if (EPI == EPI_BN_RES_RELU) {
-                        v = fmaxf(v * s_ + t_ + resid[o], 0.f);
-                    } else if (EPI == EPI_ADD) {
-                        v = v + resid[o];
-                    }
-                    out[o] = v;
-                }
-            }
-        }
-    }
-}
-
 // Per-layer launch of the halo-staged tile (pv_halo.h), in the XCD-aware tile order.
-template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, int ABL = 0, int VAR = 0>
+template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, int VAR = 0>
 __global__ __launch_bounds__(64 * NW_, 2) void conv3x3_halo(
     const float* __restrict__ in, const float* __restrict__ wp,
     const float* __restrict__ scale, const float* __restrict__ shift,
@@ -205,42 +31,30 @@ __global__ __launch_bounds__(64 * NW_, 2) void conv3x3_halo(
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NTN = C / T::BN;
     const int t = xcd_tile(blockIdx.x, gridDim.x);
-    halo_tile<C, BN_, WM_, TM_, NW_, EPI, false, ABL, VAR>(in, wp, scale, shift, resid, out,
-                                          __builtin_amdgcn_make_buffer_rsrc(out, (short)0, 0, 0x00020000), M,
-                                          (t / NTN) * T::BM, (t % NTN) * T::BN, smem, EpiX{}, ProX{}, FinX{}, guard);
+    halo_tile<C, BN_, WM_, TM_, NW_, EPI, false, VAR>(in, wp, scale, shift, resid, out,
+                                     __builtin_amdgcn_make_buffer_rsrc(out, (short)0, 0, 0x00020000), M,
+                                     (t / NTN) * T::BM, (t % NTN) * T::BN, smem, EpiX{}, ProX{}, FinX{}, guard);
 }
 
 // ---- host launchers ------------------------------------------------------
 // `c` is the launch (pv_internal.h ConvCall); every launcher hands it down unchanged.
 
-template <int C, int BN, int WM, int TM, int NW, int EPI, int SB = 0>
-static hipError_t launch_conv_t(const ConvCall& c)
-{
-    using T = ConvTile<C, BN, WM, TM, NW, SB>;
-    static bool attr_done = false;
-    if (hipError_t e = set_dynamic_lds(conv3x3_mfma<C, BN, WM, TM, NW, EPI, 0, SB>, T::LDS_BYTES, attr_done)) return e;
-    dim3 grid(((c.M + T::BM - 1) / T::BM) * (C / T::BN));
-    hipLaunchKernelGGL((conv3x3_mfma<C, BN, WM, TM, NW, EPI, 0, SB>), grid, dim3(T::NT), T::LDS_BYTES, c.st,
-                       c.in, c.wp, c.scale, c.shift, c.resid, c.out, c.M);
-    return hipGetLastError();
-}
-
-template <int C, int BN, int WM, int TM, int NW, int EPI, int VAR = 0, int ABL = 0>
+template <int C, int BN, int WM, int TM, int NW, int EPI, int VAR = 0>
 static hipError_t launch_halo_t(const ConvCall& c, const H3Guard& guard = H3Guard{})
 {
     using T = ConvTile<C, BN, WM, TM, NW>;
     constexpr int lds = halo_lds_bytes<C, BN, WM, TM, NW, VAR>();
     static bool attr_done = false;
-    if (hipError_t e = set_dynamic_lds(conv3x3_halo<C, BN, WM, TM, NW, EPI, ABL, VAR>, lds, attr_done)) return e;
+    if (hipError_t e = set_dynamic_lds(conv3x3_halo<C, BN, WM, TM, NW, EPI, VAR>, lds, attr_done)) return e;
     dim3 grid(((c.M + T::BM - 1) / T::BM) * (C / T::BN));
-    hipLaunchKernelGGL((conv3x3_halo<C, BN, WM, TM, NW, EPI, ABL, VAR>), grid, dim3(T::NT), lds, c.st, c.in, c.wp,
+    hipLaunchKernelGGL((conv3x3_halo<C, BN, WM, TM, NW, EPI, VAR>), grid, dim3(T::NT), lds, c.st, c.in, c.wp,
                        c.scale, c.shift, c.resid, c.out, c.M, guard);
     return hipGetLastError();
 }
 
 // The halo kernel's epilogues.  Only the plain body (VAR 0) is built with the residual-free
 // EPI_ADD / EPI_RAW; the variant and H3 bodies take the two eval epilogues.
-template <int C, int BN, int WM, int TM, int NW, int VAR = 0>
+template <int C, int BN, int WM, int TM, int NW = 4, int VAR = 0>
 static hipError_t launch_halo_epi(int epi, const ConvCall& c, const H3Guard& guard = H3Guard{})
 {
     if (epi == EPI_BN_RELU) return launch_halo_t<C, BN, WM, TM, NW, EPI_BN_RELU, VAR>(c, guard);
@@ -252,39 +66,20 @@ static hipError_t launch_halo_epi(int epi, const ConvCall& c, const H3Guard& gua
     return hipErrorInvalidValue;
 }
 
-int g_conv_variant = 1;   // 1: halo-staged (product); 0: per-chunk A staging (timing studies)
-
-template <int C, int BN, int WM, int TM, int NW = 4, int SB = 0>
-static hipError_t launch_conv_epi(int epi, const ConvCall& c)
-{
-    if (g_conv_variant == 1 && SB == 0) return launch_halo_epi<C, BN, WM, TM, NW>(epi, c);
-#ifdef AZG_AB_STUDIES
-    // per-chunk A staging / single-buffer tiles: A/B timing studies only
-    switch (epi) {
-        case EPI_BN_RELU: return launch_conv_t<C, BN, WM, TM, NW, EPI_BN_RELU, SB>(c);
-        case EPI_BN_RES_RELU: return launch_conv_t<C, BN, WM, TM, NW, EPI_BN_RES_RELU, SB>(c);
-        case EPI_ADD: return launch_conv_t<C, BN, WM, TM, NW, EPI_ADD, SB>(c);
-        default: return launch_conv_t<C, BN, WM, TM, NW, EPI_RAW, SB>(c);
-    }
-#else
-    return hipErrorInvalidValue;   // built without AZG_AB_STUDIES (make study)
-#endif
-}
-
 // Tile shapes {BM, BN}: index into the switch of launch_shape_c below.
 struct TileShape { int bm, bn; };
 // 0-5: 4 waves; 6-9: 8 waves (more waves per SIMD at the same LDS footprint).
-// 10-12: single LDS buffer (64x64, 128x64, 64x128; 4 waves).
 static const TileShape kShapes[] = {{128, 128}, {96, 128}, {160, 128}, {64, 128}, {128, 64}, {64, 64},
-                                    {128, 128}, {128, 128}, {128, 64}, {64, 128},
-                                    {64, 64}, {128, 64}, {64, 128}};
-constexpr int kNumShapes = (int)(sizeof(kShapes) / sizeof(kShapes[0]));
+                                    {128, 128}, {128, 128}, {128, 64}, {64, 128}};
+constexpr int kNumShapes = (int)(sizeof(kShapes) / sizeof(kShapes[0]));   // autotuning times all of them
 constexpr int kNumAutoShapes = 6;   // heuristic pick_conv_tile only considers 0-5
-constexpr int kNumTunedShapes = 10; // autotuning times 0-9 (the single-buffer 10-12 measured slower everywhere)
+// 10-12 were the single-buffer tiles (measured slower everywhere, retired): key 1 still takes
+// the numbers it took, and a launch forced to one fails with hipErrorInvalidValue
+constexpr int kLastRetiredShape = 12;
 
 static bool shape_ok(int shape, int C)
 {
-    if (shape < 0 || shape >= kNumShapes) return false;
+    if (shape < 0 || shape > kLastRetiredShape) return false;
     if (C == 64) return shape == 4 || shape == 5 || shape == 8 || shape == 10 || shape == 11;
     return true;
 }
@@ -331,7 +126,7 @@ static hipError_t launch_s8(int epi, const ConvCall& c)
         if (g_conv_var == 4) return launch_halo_epi<CC, 64, 4, 1, 8, HV_LDS_DMA>(epi, c);
         if (g_conv_var == 5) return launch_halo_epi<CC, 64, 4, 1, 8, HV_LDS_DMA | HV_BOARD_SWZ>(epi, c);
     }
-    return launch_conv_epi<CC, 64, 4, 1, 8>(epi, c);
+    return launch_halo_epi<CC, 64, 4, 1, 8>(epi, c);
 }
 
 template <int CC>
@@ -353,7 +148,7 @@ static hipError_t launch_shape8_split(int epi, const ConvCall& c)
     tail.out += off;
     tail.M = (B - B1) * PIX;
     if (hipError_t e = launch_s8<CC>(epi, head)) return e;
-    return launch_conv_epi<CC, 64, 2, 1>(epi, tail);
+    return launch_halo_epi<CC, 64, 2, 1>(epi, tail);
 }
 
 // Shape -> tile.  C = 64 has the 64-channel tiles only (0 is 4 there; 8 without the tail split).
@@ -361,28 +156,21 @@ template <int CC>
 static hipError_t launch_shape_c(int shape, int epi, const ConvCall& c)
 {
     switch (shape) {
-        case 0: return launch_conv_epi<CC, (CC < 128 ? CC : 128), 2, 2>(epi, c);
-        case 4: return launch_conv_epi<CC, 64, 2, 2>(epi, c);
-        case 5: return launch_conv_epi<CC, 64, 2, 1>(epi, c);
+        case 0: return launch_halo_epi<CC, (CC < 128 ? CC : 128), 2, 2>(epi, c);
+        case 4: return launch_halo_epi<CC, 64, 2, 2>(epi, c);
+        case 5: return launch_halo_epi<CC, 64, 2, 1>(epi, c);
         case 8:
-            if constexpr (CC == 64) return launch_conv_epi<CC, 64, 4, 1, 8>(epi, c);
+            if constexpr (CC == 64) return launch_halo_epi<CC, 64, 4, 1, 8>(epi, c);
             else return launch_shape8_split<CC>(epi, c);
-#ifdef AZG_AB_STUDIES
-        case 10: return launch_conv_epi<CC, 64, 2, 1, 4, 1>(epi, c);
-        case 11: return launch_conv_epi<CC, 64, 2, 2, 4, 1>(epi, c);
-#endif
     }
     if constexpr (CC > 64) {
         switch (shape) {
-            case 1: return launch_conv_epi<CC, 128, 1, 3>(epi, c);
-            case 2: return launch_conv_epi<CC, 128, 1, 5>(epi, c);
-            case 3: return launch_conv_epi<CC, 128, 2, 1>(epi, c);
-            case 6: return launch_conv_epi<CC, 128, 2, 2, 8>(epi, c);
-            case 7: return launch_conv_epi<CC, 128, 4, 1, 8>(epi, c);
-            case 9: return launch_conv_epi<CC, 128, 2, 1, 8>(epi, c);
-#ifdef AZG_AB_STUDIES
-            case 12: return launch_conv_epi<CC, 128, 2, 1, 4, 1>(epi, c);
-#endif
+            case 1: return launch_halo_epi<CC, 128, 1, 3>(epi, c);
+            case 2: return launch_halo_epi<CC, 128, 1, 5>(epi, c);
+            case 3: return launch_halo_epi<CC, 128, 2, 1>(epi, c);
+            case 6: return launch_halo_epi<CC, 128, 2, 2, 8>(epi, c);
+            case 7: return launch_halo_epi<CC, 128, 4, 1, 8>(epi, c);
+            case 9: return launch_halo_epi<CC, 128, 2, 1, 8>(epi, c);
         }
     }
     return hipErrorInvalidValue;
@@ -419,35 +207,6 @@ hipError_t launch_conv3x3_h3(int shape, int C, int epi, const ConvCall& c, unsig
 
 int g_conv_shape_override = -1;
 int g_conv_autotune = 1;
-int g_conv_ablation = 0;
-
-// timing-only ablations of the product tile (halo kernel, 64x64 4 waves or
-// 128x64 8 waves per g_ablation_shape; C = 128, EPI_BN_RELU launches only)
-int g_ablation_shape = 5;
-
-#ifdef AZG_AB_STUDIES
-template <int ABL>
-static hipError_t launch_ablation(const ConvCall& c)
-{
-    if (g_ablation_shape == 8) return launch_halo_t<128, 64, 4, 1, 8, EPI_BN_RELU, 0, ABL>(c);
-    return launch_halo_t<128, 64, 2, 1, 4, EPI_BN_RELU, 0, ABL>(c);
-}
-
-static hipError_t launch_ablated(const ConvCall& c)
-{
-    switch (g_conv_ablation) {
-        case 1: return launch_ablation<1>(c);
-        case 2: return launch_ablation<2>(c);
-        case 3: return launch_ablation<3>(c);
-        case 4: return launch_ablation<4>(c);
-        case 8: return launch_ablation<8>(c);
-        case 16: return launch_ablation<16>(c);
-        case 7: return launch_ablation<7>(c);
-        case 31: return launch_ablation<31>(c);
-        default: return launch_ablation<0>(c);
-    }
-}
-#endif
 
 // Autotune: the first launch for a (C, M) times every valid shape twice on the
 // real operands (each launch fully rewrites `out`, so this is idempotent) and
@@ -492,7 +251,7 @@ static int autotune_shape(int C, int epi, const ConvCall& c)
     bool ok[kNumShapes];
     for (int s = 0; s < kNumShapes; ++s) {
         best_ms[s] = 1e30f;
-        ok[s] = shape_ok(s, C) && s < kNumTunedShapes && launch_conv3x3_shape(s, C, epi, c) == hipSuccess;
+        ok[s] = shape_ok(s, C) && launch_conv3x3_shape(s, C, epi, c) == hipSuccess;
     }
     for (int r = 0; r < kTuneRounds; ++r) {
         for (int s = 0; s < kNumShapes; ++s) {
@@ -525,9 +284,6 @@ static int autotune_shape(int C, int epi, const ConvCall& c)
 
 hipError_t launch_conv3x3(int C, int epi, const ConvCall& c)
 {
-#ifdef AZG_AB_STUDIES
-    if (g_conv_ablation > 0 && C == 128 && epi == EPI_BN_RELU) return launch_ablated(c);
-#endif
     int shape = -1;
     if (g_conv_shape_override >= 0 && shape_ok(g_conv_shape_override, C)) {
         shape = g_conv_shape_override;

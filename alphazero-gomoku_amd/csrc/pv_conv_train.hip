@@ -28,9 +28,9 @@ __global__ __launch_bounds__(64 * NWT) __attribute__((amdgpu_waves_per_eu(4))) v
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NTN = C / T::BN;
     const int t = xcd_tile(blockIdx.x, gridDim.x);
-    halo_tile<C, T::BN, 4, 1, NWT, EPI, WT, 0, VAR, XE, PRO>(in, wp, oscale, nullptr, resid, out,
-                                                          wt_rsrc(out, padded_bytes(M, C)), M, (t / NTN) * T::BM,
-                                                          (t % NTN) * T::BN, smem, ex, px, fx, guard);
+    halo_tile<C, T::BN, 4, 1, NWT, EPI, WT, VAR, XE, PRO>(in, wp, oscale, nullptr, resid, out,
+                                                       wt_rsrc(out, padded_bytes(M, C)), M, (t / NTN) * T::BM,
+                                                       (t % NTN) * T::BN, smem, ex, px, fx, guard);
 }
 
 // ---- host launchers ------------------------------------------------------

@@ -46,7 +46,7 @@ struct H3Tile {
 
 // OPT bits (tile-body options, all bitwise identical): 8 = every halo row of the next
 // channel group is loaded at the group's first stage (else row i at stage i % NST);
-// 16 = the epilogue issues its residual / scale / shift loads before the LDS pass;
+// (16 was the early-epilogue form, retired with halo_epilogue's);
 // 32 = direct epilogue: every lane finishes its own accumulators (4-B loads / stores in
 // the MFMA C layout, pad rows from a per-tile LDS table) -- no LDS pass, no barrier.
 // The stage (within a group) at which halo row i of the next group is loaded:
@@ -388,8 +388,8 @@ __device__ __forceinline__ void h3_tile(const float* __restrict__ in, const floa
                                __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
-    halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, 0, BN, (OPT & 16) != 0, XE_NONE, RBUF>(acc, scale, shift, resid, out, out_rs,
-                                                                                 M, m0, n0, smem, EpiX{}, FinX{}, &guard);
+    halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, BN, XE_NONE, RBUF>(acc, scale, shift, resid, out, out_rs, M, m0, n0, smem,
+                                                                      EpiX{}, FinX{}, &guard);
 }
 
 }  // namespace azg

@@ -11,16 +11,14 @@
 #include "pv_common.h"
 #include "pv_posted.h"
 
-#ifndef AZG_EVAL_REMAT
-#define AZG_EVAL_REMAT 0   // study: 1 = per-tap addresses in the fp32 bodies too
-#endif
+
 namespace azg {
 
 // Tile shape: BM = WM*TM*32 pixels x BN channels; NW waves as WM x WN (WN = NW/WM),
 // each wave TM x TN accumulators of 32x32 (v_mfma_f32_32x32x2_f32: exact f32 FMA
 // chain -- the parity budget is 1e-5 fp32, so no bf16).  Several shapes are
 // compiled; the host picks by autotuning (all shapes are bitwise identical).
-template <int C, int BN_, int WM_, int TM_, int NW_ = 4, int SB_ = 0>
+template <int C, int BN_, int WM_, int TM_, int NW_ = 4>
 struct ConvTile {
     static constexpr int NW = NW_;                // waves per workgroup
     static constexpr int NT = 64 * NW_;           // threads
@@ -37,9 +35,6 @@ struct ConvTile {
     static constexpr int NCH = 9 * CG;
     static constexpr int A_LD = BM * BK / 4 / NT;
     static constexpr int B_LD = BN * BK / 4 / NT;
-    // SB_: single LDS buffer (the next chunk waits in registers; two barriers per
-    // chunk) -- half the LDS per workgroup, twice the resident workgroups.
-    static constexpr int LDS_BYTES = (SB_ ? 1 : 2) * (BM + BN) * LDK * 4;
     static_assert(TN >= 1 && WN * TN * 32 == BN, "bad tile");
     static_assert(A_LD >= 1 && B_LD >= 1 && A_LD * NT * 4 == BM * BK && B_LD * NT * 4 == BN * BK, "bad staging");
 };
@@ -75,7 +70,7 @@ enum HaloVar : int {
     HV_BOARD_SWZ = 1,    // halo rows swizzled on the padded board position (conflict-free fragment reads), unpadded epilogue tile
     HV_W_AHEAD2 = 2,     // weights staged two chunks ahead
     HV_LDS_DMA = 4,      // LDS-DMA staging (halo_mainloop_glds)
-    HV_EARLY_EPI = 8,    // epilogue loads issued before the LDS pass
+    // 8 was the early-epilogue study body (retired; the other bits keep their numbers)
     HV_BUF_SC1 = 16,     // buffer-resource operand addressing with sc1 loads, valid at one workgroup per CU only
     HV_BUF = 32,         // buffer-resource addressing with the default cache policy
     HV_H3 = 64,          // split-fp16 (H3): fp32-equivalent products from three fp16 MFMAs
@@ -120,7 +115,8 @@ constexpr int halo_lds_bytes()
 {
     using T = ConvTile<C, BN, WM, TM, NW>;
     const int hrg = (halo_span(T::BM) + 7) / 8 * 8;
-    const int staging = (VAR & HV_LDS_DMA) ? (2 * hrg + ((VAR & HV_W_AHEAD2) ? 3 : 2) * BN) * T::BK * 4
+    static_assert(!((VAR & HV_LDS_DMA) && (VAR & HV_W_AHEAD2)), "LDS-DMA staging has no two-ahead form");
+    const int staging = (VAR & HV_LDS_DMA) ? (2 * hrg + 2 * BN) * T::BK * 4
                                   : ((halo_span(T::BM) + T::RPP - 1) / T::RPP * T::RPP + 2 * BN) * T::BK * 4 +
                                         pro_params(PRO) * C * 4;
     const int epilogue = T::BM * (BN + 8) * 4;
@@ -273,9 +269,6 @@ __device__ __forceinline__ void bn_fin_combine8(double v0, double v1, double* re
 constexpr int PRO_NONE = 0;
 constexpr int PRO_BN = 1;       // relu(bn(z))
 constexpr int PRO_BN_RES = 2;   // relu(bn(z) + res)
-#ifndef AZG_PRO_REMAT
-#define AZG_PRO_REMAT 1
-#endif
 struct ProX {
     const float* res;     // PRO_BN_RES: residual input
     const float* scale;   // [C] BN scale of the input layer (invstd * gamma)
@@ -324,8 +317,7 @@ __device__ __forceinline__ int halo_vkey(int row)
 // guarantees every wave is past its last staging-buffer access (barrier).
 // RBUF: how the residual is read -- 0 plain pointer loads; 1 buffer loads (default
 // cache policy); 2 buffer loads with sc1 (the tower's one-workgroup-per-CU hand-off)
-template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, bool SC1, int ABL, int ELD, bool EARLY = false,
-          int XE = XE_NONE, int RBUF = 0>
+template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, bool SC1, int ELD, int XE = XE_NONE, int RBUF = 0>
 __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<C, BN_, WM_, TM_, NW_>::TN],
                                               const float* __restrict__ scale, const float* __restrict__ shift,
                                               const float* __restrict__ resid, float* __restrict__ out,
@@ -348,22 +340,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<
     const int er = tid / CPR;
     const int col = n0 + ec;
     const bool has_res = EPI == EPI_BN_RES_RELU || EPI == EPI_ADD || (EPI == EPI_BN_OPTRES_RELU && resid);
-    // EARLY: the residual / scale / shift loads are issued before the accumulator
-    // tile goes through LDS, so their latency overlaps the ds_write + barrier
-    f32x4 rve[EARLY ? NPASS : 1];
     f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, t4 = {0.f, 0.f, 0.f, 0.f};
-    if (EARLY) {
-        if (EPI == EPI_BN_RELU || EPI == EPI_BN_RES_RELU || EPI == EPI_BN_OPTRES_RELU) {
-            s4 = *(const f32x4*)(scale + col);
-            t4 = *(const f32x4*)(shift + col);
-        }
-#pragma unroll
-        for (int p = 0; p < (EARLY ? NPASS : 1); ++p) {
-            const int m = m0 + er + p * RPI;
-            rve[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (has_res && m < M) rve[p] = *(const f32x4*)(resid + pad_off(m, C) + col);
-        }
-    }
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -379,7 +356,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<
         h3s = *(const f32x4*)(scale + col);
         if (guard->dmax) h3s *= ldexpf(1.f, -h3_dgrad_exp(*guard->dmax));   // the dgrad input's 2^-k: exact
     }
-    if (!EARLY && (EPI == EPI_BN_RELU || EPI == EPI_BN_RES_RELU || EPI == EPI_BN_OPTRES_RELU)) {
+    if (EPI == EPI_BN_RELU || EPI == EPI_BN_RES_RELU || EPI == EPI_BN_OPTRES_RELU) {
         s4 = *(const f32x4*)(scale + col);
         t4 = *(const f32x4*)(shift + col);
     }
@@ -404,7 +381,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<
                                    __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (XE == XE_STATS) vk[p] = v;
-        if (m < M && (!(ABL & 16) || v[0] == 1234.5f)) {
+        if (m < M) {
             const int o = pad_off(m, C) + col;
             f32x4 xact, xz;
             if (XE == XE_BNBWD) {
@@ -412,8 +389,7 @@ __device__ __forceinline__ void halo_epilogue(const f32x16 (&acc)[TM_][ConvTile<
                 xz = *(const f32x4*)(ex.z + o);
             }
             f32x4 rv = {0.f, 0.f, 0.f, 0.f};
-            if (EARLY) rv = rve[EARLY ? p : 0];
-            else if (has_res && RBUF)   // residual produced inside the launch (tower)
+            if (has_res && RBUF)   // residual produced inside the launch (tower)
                 rv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(resid), (short)0,
                                                                                      0x7fffffff, 0x00020000),
@@ -594,13 +570,7 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
     constexpr int NBW = (NBP + NW - 1) / NW;
     constexpr int NCHK = 9 * CG;
     constexpr bool VSWZ = (VAR & HV_BOARD_SWZ) != 0;
-    // PF2 (HV_W_AHEAD2): three weight buffers, chunk j+2 issued at the top of chunk j and
-    // kept in flight across the chunk-end barrier (raw s_barrier + counted vmcnt
-    // instead of __syncthreads, whose fence drains every DMA)
-    constexpr bool PF2 = (VAR & HV_W_AHEAD2) != 0;
-    constexpr int NWB = PF2 ? 3 : 2;
-    constexpr int NPF = NP / NW;              // taps at which EVERY wave issues a halo piece
-    static_assert(!PF2 || NBP % NW == 0, "counted waits need the same weight pieces per wave");
+    static_assert((VAR & HV_W_AHEAD2) == 0, "LDS-DMA staging has no two-ahead form");
     static_assert(NPW <= 9, "halo pieces are spread over the 9 taps");
     static_assert(BN % 8 == 0, "weight pieces");
 
@@ -641,7 +611,7 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
 #pragma unroll
         for (int i = 0; i < NBW; ++i) {
             const int p = wid + NW * i;
-            if (p < NBP) glds(wk + woff[i], Bs + (j % NWB) * BN * BK + p * 8 * BK);
+            if (p < NBP) glds(wk + woff[i], Bs + (j & 1) * BN * BK + p * 8 * BK);
         }
     };
 
@@ -663,33 +633,10 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // vmcnt(n) with n an unrolled-loop constant
-    auto wait_vm = [](int n) {
-        if (n <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    };
-    auto raw_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-    };
-    // halo pieces every wave issued at chunk k (the smaller count where waves differ:
-    // a conservative wait, never a short one)
-    auto hcount = [&](int k) { return (k >= 0 && k / 9 + 1 < CG && k % 9 < NPF) ? 1 : 0; };
-
 #pragma unroll
     for (int i = 0; i < NPW; ++i) hpiece(0, i);
     bchunk(0);
-    if (PF2) {
-        bchunk(1);
-        wait_vm(NBW);            // halo of group 0 and weights of chunk 0 have landed
-        raw_barrier();
-    } else {
-        __syncthreads();
-    }
+    __syncthreads();
 
 #pragma unroll
     for (int cg = 0; cg < CG; ++cg) {
@@ -704,11 +651,7 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int j = cg * 9 + tap;
-            if (PF2) {
-                if (j + 2 < NCHK) bchunk(j + 2);
-            } else {
-                if (j + 1 < NCHK) bchunk(j + 1);
-            }
+            if (j + 1 < NCHK) bchunk(j + 1);
             if (cg + 1 < CG && tap < NPW) hpiece(cg + 1, tap);
             __builtin_amdgcn_sched_barrier(0);
             const int d = (tap / 3 - 1) * PADW + (tap % 3 - 1);
@@ -720,7 +663,7 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
                 arow[i] = r * BK;
                 aswz[i] = VSWZ ? ((vpix[i] + vd) >> 1) & 7 : (r >> 1) & 7;
             }
-            const float* Bb = Bs + (j % NWB) * BN * BK;
+            const float* Bb = Bs + (j & 1) * BN * BK;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 f32x4 a[TM], b[TN];
@@ -737,14 +680,7 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
                         for (int jn = 0; jn < TN; ++jn)
                             at[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][s], b[jn][s], at[i][jn], 0, 0, 0);
             }
-            if (PF2) {
-                // retire weights(j+1) (and, in order, everything issued before it: the
-                // next group's halo pieces); what was issued after it may stay in flight
-                wait_vm(hcount(j - 1) + (j + 2 < NCHK ? NBW : 0) + hcount(j));
-                raw_barrier();
-            } else {
-                __syncthreads();
-            }
+            __syncthreads();
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -768,13 +704,8 @@ __device__ __forceinline__ void halo_mainloop_glds(const float* __restrict__ in,
 // SC1: outputs are stored write-through (buffer_store ... sc1 via `out_rs`) so a
 // consumer workgroup of the same launch can read them after its acquire
 // (cdna_hip_programming.md Guideline 16, R1).
-//
-// ABL (timing studies only, 0 in every product launch; results are garbage when
-// set): bit 1 skips the weight loads, bit 2 the halo loads, bit 4 the per-chunk
-// barriers, bit 8 replaces LDS fragment reads by register values, bit 16 skips the
-// epilogue stores (kept live by a never-true compare).
-template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, bool SC1 = false, int ABL = 0, int VAR = 0,
-          int XE = XE_NONE, int PRO = PRO_NONE>
+template <int C, int BN_, int WM_, int TM_, int NW_, int EPI, bool SC1 = false, int VAR = 0, int XE = XE_NONE,
+          int PRO = PRO_NONE>
 __device__ __forceinline__ void halo_tile(
     const float* __restrict__ in, const float* __restrict__ wp,
     const float* __restrict__ scale, const float* __restrict__ shift,
@@ -786,7 +717,7 @@ __device__ __forceinline__ void halo_tile(
     if constexpr ((VAR & HV_LDS_DMA) != 0) {
         f32x16 acc[TM_][T::TN];
         halo_mainloop_glds<C, BN_, WM_, TM_, NW_, VAR>(in, wp, M, m0, n0, smem, acc);
-        halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, ABL, T::BN, (VAR & HV_EARLY_EPI) != 0>(
+        halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, T::BN>(
             acc, scale, shift, resid, out, out_rs, M, m0, n0, smem);
         return;
     }
@@ -801,7 +732,7 @@ __device__ __forceinline__ void halo_tile(
     static_assert(H_LD <= 9, "halo loads are spread over the 9 taps");
     static_assert(PRO == PRO_NONE || H_LD <= 8, "the operand prologue of a row runs one tap after its load");
     constexpr int kProBits = HV_H3 | HV_H3_LOLO | HV_BOARD_SWZ;   // what a prologue body may add to 0 / HV_BUF
-    static_assert(PRO == PRO_NONE || (((VAR & ~kProBits) == 0 || (VAR & ~kProBits) == HV_BUF) && ABL == 0),
+    static_assert(PRO == PRO_NONE || (VAR & ~kProBits) == 0 || (VAR & ~kProBits) == HV_BUF,
                   "operand prologue: register staging only");
     // VAR: a mask of HaloVar bits (above, with the combinations the product launches; the
     // per-layer fp32 convs use 0, key 22 = 1 HV_BOARD_SWZ).
@@ -889,7 +820,6 @@ __device__ __forceinline__ void halo_tile(
         for (int i = 0; i < H_LD; ++i) rh[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     auto hload = [&](int cg, int i) {
-        if (ABL & 2) return;
         if constexpr (HPRED) {
             if (hbase + sr + RPP * i > hmax) return;
         }
@@ -911,7 +841,6 @@ __device__ __forceinline__ void halo_tile(
                                                                          0x7fffffff, 0x00020000);
     const int wvo = ((n0 + sr) * BK + sc) * 4;
     auto bload = [&](f32x4 (&rb)[B_LD], int kc) {
-        if (ABL & 1) return;
         if constexpr ((VAR & HV_ANY_BUF) != 0) {
 #pragma unroll
             for (int i = 0; i < B_LD; ++i)
@@ -1005,7 +934,6 @@ __device__ __forceinline__ void halo_tile(
     }
     const int bswz = (r32 >> 1) & 7;
     const int brow = (wn * TN * 32 + r32) * BK;
-    const f32x4 rfix = {(float)r32, (float)h, 1.f, 2.f};   // ABL & 8 operands (timing only)
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -1040,11 +968,11 @@ __device__ __forceinline__ void halo_tile(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) at[i][j][r] = 0.f;
         const bool more = cg + 1 < CG;
-        // PRO (AZG_PRO_REMAT): the fragment row addresses are rebuilt per channel group
+        // PRO: the fragment row addresses are rebuilt per channel group
         // (a few VALU ops per tap) instead of 9 x 4 hoisted addresses living across the
         // unrolled groups -- with the prologue's registers those spilled, and every
         // reload's vmcnt wait drained the prefetch queue
-        if constexpr (PRO != PRO_NONE && AZG_PRO_REMAT) {
+        if constexpr (PRO != PRO_NONE) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(hrow[i]));
         }
@@ -1067,7 +995,7 @@ __device__ __forceinline__ void halo_tile(
             // cost the per-layer H3 tile its second workgroup per CU).  Not in the fp32
             // bodies: measured slower there (fp32 tower 82.6 vs 87.2 % of peak at B = 512
             // spill-free, the fp32 train convs +50 us per step; scripts/gpu_r5ab.sh).
-            if constexpr (H3 || AZG_EVAL_REMAT) {
+            if constexpr (H3) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(hrow[i]), "+v"(vpix[i]));
             }
@@ -1112,18 +1040,11 @@ __device__ __forceinline__ void halo_tile(
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 f32x4 a[TM], b[TN];
-                if (ABL & 8) {
 #pragma unroll
-                    for (int i = 0; i < TM; ++i) a[i] = rfix;
+                for (int i = 0; i < TM; ++i) a[i] = *(const f32x4*)(Ah + arow[i] + (((h * 4 + q) ^ aswz[i]) * 4));
+                const int rc = ((h * 4 + q) ^ bswz) * 4;
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) b[j] = rfix;
-                } else {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) a[i] = *(const f32x4*)(Ah + arow[i] + (((h * 4 + q) ^ aswz[i]) * 4));
-                    const int rc = ((h * 4 + q) ^ bswz) * 4;
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) b[j] = *(const f32x4*)(Bb + brow + j * 32 * BK + rc);
-                }
+                for (int j = 0; j < TN; ++j) b[j] = *(const f32x4*)(Bb + brow + j * 32 * BK + rc);
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -1141,7 +1062,7 @@ __device__ __forceinline__ void halo_tile(
                     for (int i = 0; i < B_LD; ++i) rb1[i] = rb2[i];
                 }
             }
-            if (!(ABL & 4)) __syncthreads();
+            __syncthreads();
             if (tap == 8 && more) {
                 hstore(cg + 1);      // every wave is past its last read of this group's halo
                 __syncthreads();
@@ -1154,7 +1075,7 @@ __device__ __forceinline__ void halo_tile(
     }
 
     // the last chunk ended with a barrier: the staging buffers are free
-    halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, ABL, (VSWZ ? BN : BN + 8), (VAR & HV_EARLY_EPI) != 0, XE,
+    halo_epilogue<C, BN_, WM_, TM_, NW_, EPI, SC1, (VSWZ ? BN : BN + 8), XE,
                   (VAR & HV_BUF_SC1) ? 2 : (VAR & HV_BUF) ? 1 : 0>(
         acc, scale, shift, resid, out, out_rs, M, m0, n0, smem, ex, fx, H3 ? &guard : nullptr);
 }

@@ -80,24 +80,18 @@ inline hipError_t set_dynamic_lds(K* kernel, int bytes, bool& done)
 // process-wide tuning variables (azg_pv_set_tuning, pv_tuning.hip: one table row per key)
 extern int g_conv_shape_override;   // pv_conv.hip
 extern int g_conv_autotune;
-extern int g_conv_ablation;
-extern int g_conv_variant;
-extern int g_ablation_shape;
 extern int g_conv_tail_split;
 extern int g_conv_var;
 extern int g_stem_variant;         // pv_stem.hip
-extern int g_stem_ablation;
 extern int g_tower_mode;           // pv_eval.hip
 extern int g_train_h3;         // pv_conv_train.hip: the train step's forward convs in split-fp16 (2: four products, 1: three, 0: fp32)
 extern int g_train_dgrad_h3;   // the train step's dgrad convs, likewise
 extern int g_tower_shape;      // pv_tower.hip
 extern int g_tower_ablation;
-extern int g_tower_var;
 extern int g_tower_group;
 extern int g_tower_h3;         // eval residual-conv arithmetic: 2 / 1 split-fp16 (16x16x32 / 32x32x16), 0 fp32
 extern int g_h3_tower_var;
 extern unsigned g_tower_wait_us;
-extern int g_tower_coh;        // study build only
 extern int g_board_abl;        // pv_board.hip (read by the study build only)
 extern int g_board16_split;    // pv_board16.hip
 extern int g_tower_breaker_s;  // pv_eval.hip: seconds of per-layer convs after a recovered launch

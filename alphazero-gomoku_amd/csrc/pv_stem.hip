@@ -91,8 +91,6 @@ __global__ __launch_bounds__(256) void stem_conv(
 // the two stems are bitwise equal (tested).  The epilogue (BN + ReLU) writes 128-B
 // runs of channels per pixel row straight from the accumulators.
 constexpr int STEM_CW = 64;   // channels per wave (2 accumulators): twice the waves of 128
-// ABL (timing studies only, results invalid when set): 1 no stores, 2 no input
-// loads, 4 no weight loads, 8 no MFMA.
 // STATS (train forward, EPI_RAW): per 128-row tile (the workgroup's 4 waves) and channel
 // the mean and M2 of the raw stem output straight from the accumulators (two-pass, fp32)
 // -> pa / pb [tile][C], combined exactly in fp64 by bn_fin_tiles_kernel (prow 128): the
@@ -101,7 +99,7 @@ constexpr int STEM_CW = 64;   // channels per wave (2 accumulators): twice the w
 // cells as boards[board_of(i)][sym_src(yy, xx, s_i)] -- board_of(i) = i, s_i = syms[i] & 7
 // (SYM_EACH) or board_of(i) = i / 8, s_i = i % 8 (SYM_MEAN8).  Off-board handling and the
 // arithmetic are the BOARDS path's; a template flag, so SYM_NONE compiles to what it was.
-template <int C, int EPI, bool BOARDS, int ABL = 0, bool STATS = false, int SYM = SYM_NONE>
+template <int C, int EPI, bool BOARDS, bool STATS = false, int SYM = SYM_NONE>
 __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, const int8_t* __restrict__ boards,
                                                  const int8_t* __restrict__ players, const float* __restrict__ ws,
                                                  const float* __restrict__ scale, const float* __restrict__ shift,
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, co
         const int k = 2 * s + h;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-            bw[j][s] = (ABL & 4) ? (float)(k + j) : (k < 27 ? ws[k * C + c0 + 32 * j + r32] : 0.f);
+            bw[j][s] = k < 27 ? ws[k * C + c0 + 32 * j + r32] : 0.f;
     }
 
     const int m = min(m0 + r32, M - 1);
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, co
             const bool in = yy >= 0 && yy < BOARD && xx >= 0 && xx < BOARD;
 #pragma unroll
             for (int ci = 0; ci < 3; ++ci)
-                nb[ci][t] = (ABL & 2) ? (float)(yy + xx + ci) : (in ? xb[ci * PIX + yy * BOARD + xx] : 0.f);
+                nb[ci][t] = in ? xb[ci * PIX + yy * BOARD + xx] : 0.f;
         }
     }
     float av[KS];
@@ -176,10 +174,7 @@ __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, co
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (ABL & 8) acc[j][s] = av[s] * bw[j][s];
-            else acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[j][s], acc[j], 0, 0, 0);
-        }
+        for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bw[j][s], acc[j], 0, 0, 0);
 
     // epilogue through a wave-private LDS tile [32 px][32 ch] per accumulator: lane
     // (p = lane/8 + 8*it, 16-B run lane%8) finishes 4 channels of one pixel and
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, co
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             f32x4 v = *(const f32x4*)(&E[(lane >> 3) + 8 * it][ec]);
-            if (orow[it] >= 0 && (!(ABL & 1) || v[0] == 1234.5f)) {
+            if (orow[it] >= 0) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (EPI == EPI_BN_RELU) v[e] = fmaxf(v[e] * s4[e] + t4[e], 0.f);
@@ -263,7 +258,6 @@ __global__ __launch_bounds__(256) void stem_mfma(const float* __restrict__ x, co
 // ---- host launchers ------------------------------------------------------
 
 int g_stem_variant = 1;   // 1: fp32-MFMA stem (product); 0: VALU stem_conv (bitwise reference)
-int g_stem_ablation = 0;  // timing studies only (C = 128 float-plane stem)
 
 // stem_mfma's grid: 128 pixels (4 waves of 32) x STEM_CW channels per workgroup
 static dim3 stem_grid(int C, int B)
@@ -280,9 +274,9 @@ hipError_t launch_stem_stats(int C, const float* x, const float* ws, float* out,
     const int M = B * PIX;
     const dim3 grid = stem_grid(C, B);
     switch (C) {
-        case 64: hipLaunchKernelGGL((stem_mfma<64, EPI_RAW, false, 0, true>), grid, dim3(256), 0, st, x, nullptr, nullptr, ws, nullptr, nullptr, out, M, pa, pb); break;
-        case 128: hipLaunchKernelGGL((stem_mfma<128, EPI_RAW, false, 0, true>), grid, dim3(256), 0, st, x, nullptr, nullptr, ws, nullptr, nullptr, out, M, pa, pb); break;
-        case 256: hipLaunchKernelGGL((stem_mfma<256, EPI_RAW, false, 0, true>), grid, dim3(256), 0, st, x, nullptr, nullptr, ws, nullptr, nullptr, out, M, pa, pb); break;
+        case 64: hipLaunchKernelGGL((stem_mfma<64, EPI_RAW, false, true>), grid, dim3(256), 0, st, x, nullptr, nullptr, ws, nullptr, nullptr, out, M, pa, pb); break;
+        case 128: hipLaunchKernelGGL((stem_mfma<128, EPI_RAW, false, true>), grid, dim3(256), 0, st, x, nullptr, nullptr, ws, nullptr, nullptr, out, M, pa, pb); break;
+        case 256: hipLaunchKernelGGL((stem_mfma<256, EPI_RAW, false, true>), grid, dim3(256), 0, st, x, nullptr, nullptr, ws, nullptr, nullptr, out, M, pa, pb); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -305,28 +299,12 @@ static hipError_t launch_stem_c(int epi, const float* x, const float* ws, const 
     };
     const bool use_mfma = g_stem_variant == 1;
     if (symmode == SYM_EACH) {
-        if (use_mfma) mfma(stem_mfma<CC, EPI_BN_RELU, true, 0, false, SYM_EACH>);
+        if (use_mfma) mfma(stem_mfma<CC, EPI_BN_RELU, true, false, SYM_EACH>);
         else valu(stem_conv<CC, EPI_BN_RELU, true, SYM_EACH>);
     } else if (symmode == SYM_MEAN8) {
-        if (use_mfma) mfma(stem_mfma<CC, EPI_BN_RELU, true, 0, false, SYM_MEAN8>);
+        if (use_mfma) mfma(stem_mfma<CC, EPI_BN_RELU, true, false, SYM_MEAN8>);
         else valu(stem_conv<CC, EPI_BN_RELU, true, SYM_MEAN8>);
     } else if (use_mfma) {
-#ifdef AZG_AB_STUDIES
-        if constexpr (CC == 128) {
-            if (g_stem_ablation && !boards && epi == EPI_BN_RELU) {
-                switch (g_stem_ablation) {
-                    case 1: mfma(stem_mfma<128, EPI_BN_RELU, false, 1>); break;
-                    case 2: mfma(stem_mfma<128, EPI_BN_RELU, false, 2>); break;
-                    case 4: mfma(stem_mfma<128, EPI_BN_RELU, false, 4>); break;
-                    case 8: mfma(stem_mfma<128, EPI_BN_RELU, false, 8>); break;
-                    case 6: mfma(stem_mfma<128, EPI_BN_RELU, false, 6>); break;
-                    case 14: mfma(stem_mfma<128, EPI_BN_RELU, false, 14>); break;
-                    case 15: mfma(stem_mfma<128, EPI_BN_RELU, false, 15>); break;
-                }
-                return hipGetLastError();
-            }
-        }
-#endif
         if (boards) mfma(stem_mfma<CC, EPI_BN_RELU, true>);
         else if (epi == EPI_RAW) mfma(stem_mfma<CC, EPI_RAW, false>);
         else mfma(stem_mfma<CC, EPI_BN_RELU, false>);

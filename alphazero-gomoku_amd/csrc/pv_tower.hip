@@ -24,8 +24,7 @@
 //    at launch): s_waitcnt vmcnt(0), workgroup barrier, and EVERY load of handed-off
 //    bytes (halo rows, the epilogue's residual) is a 16-B sc1 buffer load -- row 1 of
 //    the guide's measured hand-off table, which requires one workgroup per CU in
-//    every cell; no LDS-DMA or early-epilogue path may be combined with it
-//    (static_assert below).
+//    every cell; no LDS-DMA path may be combined with it (static_assert below).
 // Deadlock freedom: a tile waits only on tiles claimed before it (all of layer
 // l-1 precedes layer l in claim order), and a claimed tile is always executed by a
 // running workgroup, so the oldest unfinished tile can always finish.  Waits are
@@ -68,15 +67,12 @@ struct TowerArgs {
     int group;           // 1: a claim is one (M, N) tile; NTN: one M tile with all its N
                          // tiles, run back to back by the claiming workgroup (the second
                          // N tile's halo rows are hits in that XCD's L2)
-    int abl;             // timing studies only (0 in the product; results not valid otherwise):
+    int abl;             // timing studies only (key 8; 0 in the product, results not valid otherwise):
                          // bit 1 skips the dependency wait + acquire, bit 2 the publish drain
 };
 
 unsigned g_tower_wait_us = kTowerWaitUs;     // tuning key 14 (tests: 0 forces the timeout path)
 int g_tower_group = 1;                       // tuning key 17: 1 (default) = claim an M tile with all its N tiles
-#ifdef AZG_AB_STUDIES
-int g_tower_coh = 0;   // study key 31: sc1 dependent loads with 64x64 / 128x64 tiles (OUTSIDE the guide's envelope)
-#endif
 
 // waves per SIMD the register budget is sized for: 4 (128 VGPRs) for the one-
 // accumulator tiles (two 8-wave or four 4-wave workgroups per CU, or the one 16-wave
@@ -211,14 +207,12 @@ __device__ __noinline__ void tower_timeout(unsigned* ring, unsigned* d, const un
     st(TD_PSTART, started ? ld(pp + 3) - (unsigned)t0 : 0u);   // signed on the host
 }
 
-// HABL (study build, timing / traffic ablations only: results invalid): halo_tile's ABL
-// bits -- 1 skips the weight loads, 2 the halo loads
-template <int C, int BN_, int WM_, int TM_, int NW_, int VAR = 0, int HABL = 0>
+template <int C, int BN_, int WM_, int TM_, int NW_, int VAR>
 __global__ __launch_bounds__(64 * NW_, (tower_min_waves<BN_, NW_>())) void conv_tower(const TowerArgs a)
 {
     using T = ConvTile<C, BN_, WM_, TM_, NW_>;
-    static_assert(!((VAR & HV_ANY_BUF) && (VAR & (HV_LDS_DMA | HV_EARLY_EPI))),
-                  "buffer halo / residual loads (HV_BUF_SC1, HV_BUF) exclude HV_LDS_DMA and HV_EARLY_EPI");
+    static_assert(!((VAR & HV_ANY_BUF) && (VAR & HV_LDS_DMA)),
+                  "buffer halo / residual loads (HV_BUF_SC1, HV_BUF) exclude HV_LDS_DMA");
     constexpr int NTN = C / T::BN;
     constexpr int LDS_FLOATS = tower_body_lds<C, BN_, WM_, TM_, NW_, VAR>() / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -285,7 +279,7 @@ __global__ __launch_bounds__(64 * NW_, (tower_min_waves<BN_, NW_>())) void conv_
                     Ly.in, Ly.wp, Ly.scale, Ly.shift, Ly.resid, Ly.out, rs, a.M, mt * T::BM, nt * T::BN, smem,
                     H3Guard{a.ring_ovf, a.seq});
             else
-                halo_tile<C, BN_, WM_, TM_, NW_, EPI_BN_OPTRES_RELU, true, HABL, VAR>(
+                halo_tile<C, BN_, WM_, TM_, NW_, EPI_BN_OPTRES_RELU, true, VAR>(
                     Ly.in, Ly.wp, Ly.scale, Ly.shift, Ly.resid, Ly.out, rs, a.M, mt * T::BM, nt * T::BN, smem, EpiX{},
                     ProX{}, FinX{}, H3Guard{a.ring_ovf, a.seq});
         }
@@ -299,38 +293,32 @@ __global__ __launch_bounds__(64 * NW_, (tower_min_waves<BN_, NW_>())) void conv_
     }
 }
 
-template <int C, int BN, int WM, int TM, int NW, int VAR = 0, int HABL = 0>
+template <int C, int BN, int WM, int TM, int NW, int VAR>
 static hipError_t launch_tower_t(const TowerArgs& a, hipStream_t st, int* grid_out)
 {
     constexpr int lds = tower_lds_bytes<C, BN, WM, TM, NW, VAR>();
     static int grid = 0;
     if (grid == 0) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_tower<C, BN, WM, TM, NW, VAR, HABL>,
+        hipError_t e = hipFuncSetAttribute((const void*)conv_tower<C, BN, WM, TM, NW, VAR>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
         int per_cu = 0, dev = 0, cus = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_tower<C, BN, WM, TM, NW, VAR, HABL>,
-                                                         64 * NW, lds);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_tower<C, BN, WM, TM, NW, VAR>, 64 * NW,
+                                                         lds);
         if (e != hipSuccess) return e;
         if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
         if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        // the sc1-load hand-off (HV_BUF_SC1) is valid at one workgroup per CU only: the
-        // product refuses to launch it at any other residency (the study build runs the
-        // round-2 two-per-CU form on purpose, key 31)
-#ifndef AZG_AB_STUDIES
+        // the sc1-load hand-off (HV_BUF_SC1) is valid at one workgroup per CU only: refused
+        // at any other residency
         if ((VAR & HV_BUF_SC1) && per_cu != 1) return hipErrorInvalidConfiguration;
-#else
-        if ((VAR & HV_BUF_SC1) && NW >= 16 && per_cu != 1) return hipErrorInvalidConfiguration;
-#endif
         grid = max(1, per_cu) * cus;
     }
     if (grid_out) *grid_out = grid;
-    hipLaunchKernelGGL((conv_tower<C, BN, WM, TM, NW, VAR, HABL>), dim3(grid), dim3(64 * NW), lds, st, a);
+    hipLaunchKernelGGL((conv_tower<C, BN, WM, TM, NW, VAR>), dim3(grid), dim3(64 * NW), lds, st, a);
     return hipGetLastError();
 }
 
-int g_tower_ablation = 0;
-int g_tower_var = 0;     // study body of the 128x64 C=128 tower (0 = product; 1..8, 12: that HaloVar mask; 13-16 below)
+int g_tower_ablation = 0;   // key 8 (study build): TowerArgs::abl
 int g_tower_shape = 8;   // forced shape when g_tower_mode == 1: 5 = 64x64 (4 waves), 8 = 128x64 (8 waves),
                          // 10 = 128x128 (16 waves, one workgroup per CU; C = 128)
 
@@ -378,9 +366,7 @@ hipError_t launch_tower(int C, int NB, int shape, float* const act[3], const flo
     unsigned* sync = ts.sync;
     a.group = g_tower_group ? C / (shape == 8 || shape == 5 ? 64 : 128) : 1;
     if (shape == 12 && !h3) return hipErrorInvalidValue;   // h3_tile: split-fp16 only
-#ifndef AZG_AB_STUDIES
     if (shape == 10 && C != 128) return hipErrorInvalidValue;   // 16-wave tile: C = 128 only (C = 256 spills)
-#endif
     a.abl = g_tower_ablation;
     float* X = act[0];
     float* H = act[1];
@@ -425,54 +411,6 @@ hipError_t launch_tower(int C, int NB, int shape, float* const act[3], const flo
             default: return hipErrorInvalidValue;
         }
     }
-#ifdef AZG_AB_STUDIES
-    // traffic ablations of the 128x64 tower (key 8 bits 4 / 8: no weight / no halo loads)
-    if (shape == 8 && (a.abl & 12)) {
-        const bool nw = a.abl & 4, nh = a.abl & 8;
-        if (C == 256 && nw && nh) return launch_tower_t<256, 64, 4, 1, 8, HV_BUF, 3>(a, st, nullptr);
-        if (C == 256 && nw) return launch_tower_t<256, 64, 4, 1, 8, HV_BUF, 1>(a, st, nullptr);
-        if (C == 256 && nh) return launch_tower_t<256, 64, 4, 1, 8, HV_BUF, 2>(a, st, nullptr);
-        if (C == 128 && nw && nh) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF, 3>(a, st, nullptr);
-        if (C == 128 && nw) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF, 1>(a, st, nullptr);
-        if (C == 128 && nh) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF, 2>(a, st, nullptr);
-    }
-    if (g_tower_coh && (shape == 8 || shape == 5)) {   // study only: sc1 loads at 2-4 workgroups per CU
-        if (C == 128 && shape == 8) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF_SC1>(a, st, nullptr);
-        if (C == 128) return launch_tower_t<128, 64, 2, 1, 4, HV_BUF_SC1>(a, st, nullptr);
-    }
-    if (C == 128 && shape == 9) {   // 128x128 tiles, 2 accumulators per wave, LDS-DMA staging (A/B study)
-        if (g_tower_var == 5) return launch_tower_t<128, 128, 4, 1, 8, HV_LDS_DMA | HV_BOARD_SWZ>(a, st, nullptr);
-        return launch_tower_t<128, 128, 4, 1, 8, HV_LDS_DMA>(a, st, nullptr);
-    }
-    if (C == 128 && shape == 8 && g_tower_var != 0) {   // A/B variants (bitwise identical)
-        if (g_tower_var == 3) return launch_tower_t<128, 64, 4, 1, 8, HV_W_AHEAD2 | HV_BOARD_SWZ>(a, st, nullptr);
-        if (g_tower_var == 1) return launch_tower_t<128, 64, 4, 1, 8, HV_BOARD_SWZ>(a, st, nullptr);
-        if (g_tower_var == 2) return launch_tower_t<128, 64, 4, 1, 8, HV_W_AHEAD2>(a, st, nullptr);
-        if (g_tower_var == 4) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA>(a, st, nullptr);
-        if (g_tower_var == 5) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA | HV_BOARD_SWZ>(a, st, nullptr);
-        if (g_tower_var == 8) return launch_tower_t<128, 64, 4, 1, 8, HV_EARLY_EPI>(a, st, nullptr);
-        if (g_tower_var == 6) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA | HV_W_AHEAD2>(a, st, nullptr);
-        if (g_tower_var == 7) return launch_tower_t<128, 64, 4, 1, 8, HV_LDS_DMA | HV_W_AHEAD2 | HV_BOARD_SWZ>(a, st, nullptr);
-        if (g_tower_var == 12) return launch_tower_t<128, 64, 4, 1, 8, HV_EARLY_EPI | HV_LDS_DMA>(a, st, nullptr);
-        if (g_tower_var == 14) return launch_tower_t<128, 64, 4, 1, 8, kHaloTower256>(a, st, nullptr);
-        if (g_tower_var == 15) return launch_tower_t<128, 64, 4, 1, 8, HV_BUF | HV_W_AHEAD2>(a, st, nullptr);
-    }
-    if (C == 256 && shape == 8 && g_tower_var == 2)   // weights staged two chunks ahead, C = 256
-        return launch_tower_t<256, 64, 4, 1, 8, HV_BUF | HV_W_AHEAD2>(a, st, nullptr);
-    if (C == 256 && shape == 8 && g_tower_var == 16)   // round-3 product body at C = 256
-        return launch_tower_t<256, 64, 4, 1, 8, HV_BUF>(a, st, nullptr);
-    if (C == 256 && shape == 5 && g_tower_var == 16)   // round-3 64x64 body at C = 256
-        return launch_tower_t<256, 64, 2, 1, 4, HV_BUF>(a, st, nullptr);
-    if (C == 256 && shape == 10) {   // 16-wave 128x128 tile at C = 256 (spills; traffic study)
-        if (g_tower_var == 1) return launch_tower_t<256, 128, 4, 1, 16, HV_BUF>(a, st, nullptr);
-        return launch_tower_t<256, 128, 4, 1, 16, HV_BUF_SC1>(a, st, nullptr);
-    }
-    if (C == 128 && shape == 5 && g_tower_var == 14) return launch_tower_t<128, 64, 2, 1, 4, kHaloTower256>(a, st, nullptr);
-    if (C == 128 && shape == 10 && g_tower_var == 1)   // 16-wave tile with the acquire instead of sc1 loads
-        return launch_tower_t<128, 128, 4, 1, 16, HV_BUF>(a, st, nullptr);
-    if (C == 128 && shape == 8 && g_tower_var == 13)   // round-2 acquire form: 64-bit pointer loads (no HaloVar bit)
-        return launch_tower_t<128, 64, 4, 1, 8, 0>(a, st, nullptr);
-#endif
     switch (C) {
         case 64:
             if (shape == 8) return launch_tower_t<64, 64, 4, 1, 8, HV_BUF>(a, st, nullptr);

@@ -20,8 +20,7 @@ bool flag(int& v) { v = v ? 1 : 0; return true; }
 bool zero_one(int& v) { return v == 0 || v == 1; }
 bool upto2(int& v) { return v >= 0 && v <= 2; }
 bool nonneg(int& v) { return v >= 0; }
-bool tower_shape(int& v) { return v == 5 || v == 8 || v == 10 || (v >= 12 && v <= 14) || (kStudy && v == 9); }
-bool tower_body(int& v) { return kStudy ? (v >= 0 && v <= 8) || (v >= 12 && v <= 16) : v == 0; }
+bool tower_shape(int& v) { return v == 5 || v == 8 || v == 10 || (v >= 12 && v <= 14); }
 bool conv_body(int& v) { return v == 0 || v == 1 || v == 4 || v == 5; }
 bool wgrad_splits(int& v) { return v == 0 || (v >= 8 && v <= 64 && v % 8 == 0); }
 
@@ -35,15 +34,10 @@ struct Row {
 const Row kRows[] = {
     {AZG_PV_TUNE_CONV_SHAPE, &g_conv_shape_override, any, true},
     {AZG_PV_TUNE_CONV_AUTOTUNE, &g_conv_autotune, any, true},
-    {AZG_PV_TUNE_CONV_ABLATION, &g_conv_ablation, any, false},
-    {AZG_PV_TUNE_CONV_STAGING, &g_conv_variant, any, false},
     {AZG_PV_TUNE_TOWER_MODE, &g_tower_mode, any, true},
     {AZG_PV_TUNE_TOWER_SHAPE, &g_tower_shape, tower_shape, true},
-    {AZG_PV_TUNE_ABLATION_SHAPE, &g_ablation_shape, any, false},
     {AZG_PV_TUNE_TOWER_ABLATION, &g_tower_ablation, any, false},
     {AZG_PV_TUNE_STEM_KERNEL, &g_stem_variant, zero_one, true},
-    {AZG_PV_TUNE_TOWER_BODY, &g_tower_var, tower_body, true},
-    {AZG_PV_TUNE_STEM_ABLATION, &g_stem_ablation, any, false},
     {AZG_PV_TUNE_TOWER_CLAIM, &g_tower_group, zero_one, true},
     {AZG_PV_TUNE_BREAKER_SECONDS, &g_tower_breaker_s, nonneg, true},
     {AZG_PV_TUNE_EVAL_ARITH, &g_tower_h3, upto2, true},
@@ -63,6 +57,13 @@ const Row kRows[] = {
     {AZG_PV_TUNE_BOARD16_SPLIT_MAX, &g_board16_split, nonneg, true},
 };
 
+// Retired keys (finished conv-tile studies): they set nothing and return what the product
+// library always returned for them.
+const struct { int key, value; } kRetired[] = {
+    {AZG_PV_TUNE_CONV_ABLATION, 0}, {AZG_PV_TUNE_CONV_STAGING, 1}, {AZG_PV_TUNE_ABLATION_SHAPE, 5},
+    {AZG_PV_TUNE_TOWER_BODY, 0},    {AZG_PV_TUNE_STEM_ABLATION, 0}, {AZG_PV_TUNE_TOWER_SC1_LOADS, 0},
+};
+
 }  // namespace
 
 extern "C" int32_t azg_pv_set_tuning(int32_t key, int32_t value)
@@ -77,15 +78,6 @@ extern "C" int32_t azg_pv_set_tuning(int32_t key, int32_t value)
             g_tower_wait_us = value < 0 ? kTowerWaitUs : (unsigned)value;
             return prev;
         }
-        case AZG_PV_TUNE_TOWER_SC1_LOADS: {   // outside the guide's measured envelope: never in the product
-#ifdef AZG_AB_STUDIES
-            const int prev = g_tower_coh;
-            g_tower_coh = value ? 1 : 0;
-            return prev;
-#else
-            return 0;
-#endif
-        }
     }
     for (const Row& r : kRows) {
         if (r.key != key) continue;
@@ -94,5 +86,7 @@ extern "C" int32_t azg_pv_set_tuning(int32_t key, int32_t value)
         if ((r.product || kStudy) && r.rule(v)) *r.var = v;
         return prev;
     }
+    for (const auto& r : kRetired)
+        if (r.key == key) return r.value;
     return -1;
 }

@@ -341,7 +341,9 @@ int32_t azg_pv_profile_read(azg_pv* h, double* ms, int64_t* launches);
 int32_t azg_pv_profile_boards(const azg_pv* h, int64_t* boards);
 
 /* Keys of azg_pv_set_tuning: process-wide tuning knobs (benchmarks / A-B tests).  The
- * numbers are frozen: benchmarks and scripts pass them as integers. */
+ * numbers are frozen: benchmarks and scripts pass them as integers.  A retired key
+ * belonged to a finished timing study: it sets nothing, in any build, and returns the
+ * constant given with it. */
 enum azg_pv_tuning_key {
     /* force the 3x3-conv tile shape index (-1 = automatic) */
     AZG_PV_TUNE_CONV_SHAPE = 0,
@@ -351,11 +353,10 @@ enum azg_pv_tuning_key {
     AZG_PV_TUNE_CONV_AUTOTUNE = 1,
     /* query the tuned shape for value = M*1024 + C (-1 if not tuned yet) */
     AZG_PV_TUNE_QUERY_CONV_SHAPE = 2,
-    /* timing-only ablation mask of the per-layer conv (results invalid while set);
-     * study build only: the product library ignores a set */
+    /* retired (ablation mask of the per-layer conv): returns 0 */
     AZG_PV_TUNE_CONV_ABLATION = 3,
-    /* conv kernel variant (1 halo-staged, default; 0 per-chunk staging, timing only);
-     * study build only: the product library ignores a set */
+    /* retired (per-chunk staging against the halo-staged kernel, the only one now):
+     * returns 1 */
     AZG_PV_TUNE_CONV_STAGING = 4,
     /* eval residual tower: 0 one launch per conv, 1 one persistent launch (shape from
      * TOWER_SHAPE), 2 (default) chosen per (C, blocks, batch bucket) by timing every
@@ -369,18 +370,17 @@ enum azg_pv_tuning_key {
      * the current arithmetic lacks runs as 8); with EVAL_ARITH = 2 at C = 128
      * TOWER_MODE / TOWER_SHAPE do not apply (one form: the 16x16x32 board tower) */
     AZG_PV_TUNE_TOWER_SHAPE = 6,
-    /* tile shape (5 or 8) the timing-only ablations run; study build only */
+    /* retired (tile shape of the per-layer conv ablations): returns 5 */
     AZG_PV_TUNE_ABLATION_SHAPE = 7,
-    /* timing-only ablation mask of the persistent tower (results invalid while set);
-     * study build only */
+    /* timing-only ablation mask of the persistent tower (1 no dependency wait, 2 no
+     * publish drain; results invalid while set); study build only */
     AZG_PV_TUNE_TOWER_ABLATION = 8,
     /* stem kernel (1 = fp32 MFMA, default; 0 = VALU reference, bitwise equal) */
     AZG_PV_TUNE_STEM_KERNEL = 9,
-    /* tile-body variant of the C=128 128x64 persistent tower (0 = default; the study
-     * build also takes 1..8 and 12..16 = swizzle / prefetch / LDS-DMA staging variants
-     * for A/B timing, all bitwise identical to 0) */
+    /* retired (tile-body variants of the persistent tower; none beat the default):
+     * returns 0 */
     AZG_PV_TUNE_TOWER_BODY = 10,
-    /* stem ablation mask (timing only, results invalid while set); study build only */
+    /* retired (stem ablation mask): returns 0 */
     AZG_PV_TUNE_STEM_ABLATION = 11,
     /* persistent-tower dependency wait bound in microseconds of the waiting wave's
      * awake time (default 100000 = 100 ms; -1 restores it; 0 makes every dependency
@@ -434,10 +434,10 @@ enum azg_pv_tuning_key {
     /* train conv weight-grad pixel splits (0 = automatic, default; 8..64, a multiple
      * of 8); bitwise identical only at a fixed value */
     AZG_PV_TUNE_WGRAD_SPLITS = 27,
-    /* study build only: the 64x64 / 128x64 towers with sc1 dependent loads and no
-     * acquire (two or more workgroups per CU: outside the microarch guide's measured
-     * envelope; the product uses the acquire there and the sc1 form only for the
-     * one-workgroup-per-CU 16-wave tile); returns 0 in the product library */
+    /* retired (the 64x64 / 128x64 towers with sc1 dependent loads and no acquire, at
+     * two or more workgroups per CU: outside the microarch guide's measured envelope;
+     * the acquire is used there and the sc1 form only for the one-workgroup-per-CU
+     * 16-wave tile): returns 0 */
     AZG_PV_TUNE_TOWER_SC1_LOADS = 31,
     /* train BN apply / BN-backward apply passes: workgroup cap of their grid-stride
      * launch (0 = four float4 per thread, default); bitwise identical */

@@ -24,9 +24,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--shape", type=int, default=-1, help="force the per-layer tile shape (key 0)")
     ap.add_argument("--tower-shape", type=int, default=8, help="persistent tower tile shape (key 6)")
-    ap.add_argument("--var", type=int, default=0, help="study build: tower tile-body variant (key 10)")
-    ap.add_argument("--coh", type=int, default=0, help="study build: round-2 sc1 tower hand-off at 2 WG/CU (key 31)")
-    ap.add_argument("--abl", type=int, default=0, help="study build: tower ablation bits (key 8; 4 no weight loads, 8 no halo loads)")
+    ap.add_argument("--abl", type=int, default=0, help="study build: tower ablation bits (key 8; 1 no dependency wait, 2 no publish drain)")
     ap.add_argument("--group", type=int, default=1, help="tower claims (key 17: 0 tile, 1 M tile)")
     ap.add_argument("--board-abl", type=int, default=0, help="board tower timing ablations (key 51; results invalid)")
     ap.add_argument("--blocks", type=int, default=6)
@@ -38,8 +36,6 @@ def main():
     lib.azg_pv_set_tuning(5, args.tower)
     lib.azg_pv_set_tuning(6, args.tower_shape)
     lib.azg_pv_set_tuning(0, args.shape)
-    lib.azg_pv_set_tuning(10, args.var)
-    lib.azg_pv_set_tuning(31, args.coh)
     lib.azg_pv_set_tuning(8, args.abl)
     lib.azg_pv_set_tuning(17, args.group)
     if args.board_abl:
@@ -77,7 +73,6 @@ def main():
             out[k]["mfma_frac"] = round(per / (ms / n / 1e3) / 157.3e12, 4)
     if args.check:
         lib.azg_pv_set_tuning(6, 8)
-        lib.azg_pv_set_tuning(10, 0)
         p8, v8 = torch.empty_like(probs), torch.empty_like(values)
         eng.forward_into(x, p8, v8)
         torch.cuda.synchronize()

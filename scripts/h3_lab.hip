@@ -42,7 +42,7 @@ __global__ __launch_bounds__(64 * NW_, WPE) void lab_conv(const float* __restric
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NTN = C / T::BN;
     const int t = xcd_tile(blockIdx.x, gridDim.x);
-    halo_tile<C, BN_, WM_, TM_, NW_, EPI_BN_RES_RELU, false, 0, VAR>(
+    halo_tile<C, BN_, WM_, TM_, NW_, EPI_BN_RES_RELU, false, VAR>(
         in, wp, scale, shift, resid, out, __builtin_amdgcn_make_buffer_rsrc(out, (short)0, 0, 0x00020000), M,
         (t / NTN) * T::BM, (t % NTN) * T::BN, smem, EpiX{}, ProX{}, FinX{}, guard);
 }
@@ -315,10 +315,9 @@ static std::vector<Variant> variants()
         VH(C, 128, 4, 1, 8, 1, 2, 2),    // 128x128, 8 waves, wave 32x64
         VH(C, 128, 2, 2, 8, 1, 2, 2),    // 128x128, 8 waves as 2x4, wave 64x32
         VH(C, 128, 2, 2, 4, 3, 2, 1),    // 128x128, wave 64x64, 3-tap stages, one workgroup per CU
-        // OPT (ablation value bits >= 8): 8 = next-group halo loads at the group's first stage,
-        // 16 = epilogue residual loads before the LDS pass -- bitwise identical
-        VA(C, 128, 2, 2, 4, 1, 3, 2, 8), VA(C, 128, 2, 2, 4, 1, 3, 2, 16), VA(C, 128, 2, 2, 4, 1, 3, 2, 24),
-        VA(C, 64, 4, 1, 8, 3, 2, 2, 8), VA(C, 64, 4, 1, 8, 3, 2, 2, 24), VA(C, 64, 4, 1, 8, 1, 3, 4, 24),
+        // OPT (ablation value bits >= 8): 8 = next-group halo loads at the group's first stage
+        // -- bitwise identical
+        VA(C, 128, 2, 2, 4, 1, 3, 2, 8), VA(C, 64, 4, 1, 8, 3, 2, 2, 8), VA(C, 64, 4, 1, 8, 1, 3, 4, 8),
         // OPT 32: direct epilogue (no LDS pass)
         VA(C, 128, 2, 2, 4, 1, 3, 2, 32), VA(C, 128, 4, 1, 8, 1, 2, 4, 32), VA(C, 64, 4, 1, 8, 3, 2, 2, 32),
         // 128x128 / 8 waves (wave 32x64) capped at 128 VGPRs: two workgroups per CU

@@ -6,7 +6,7 @@ wall time, per batch size and tower tile shape.
 """
 import os as _os
 
-# A/B study variants live only in the study build (make -C alphazero-gomoku_amd/csrc study)
+# the tower ablations (key 8) live only in the study build (make -C alphazero-gomoku_amd/csrc study)
 _os.environ.setdefault("AZG_PV_LIB", _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))),
                                                    "alphazero-gomoku_amd", "libazg_pv_study.so"))
 import argparse
@@ -29,7 +29,6 @@ def main():
     ap.add_argument("--channels", type=int, default=128)
     ap.add_argument("--ablations", default="", help="comma list of tower ablation masks to time too")
     ap.add_argument("--shapes", default="", help="extra tower tile shapes")
-    ap.add_argument("--vars", default="", help="tower tile-body variants (C=128, 128x64 tiles): 0..5")
     args = ap.parse_args()
     from network import PyTorchModel
     from synth import synth_encoded
@@ -46,16 +45,13 @@ def main():
         values = torch.empty((B, 1), device="cuda")
         flop = 2 * 225 * C * 9 * C * B * 2 * args.blocks
         row = {"batch": B}
-        variants = [("layers", 0, 5, 0, 0), ("tower64", 1, 5, 0, 0), ("tower128", 1, 8, 0, 0),
-                    ("tower128_group", 1, 8, 0, 0)]
-        variants += [(f"tower128_abl{a}", 1, 8, int(a), 0) for a in args.ablations.split(",") if a]
-        variants += [(f"tower_s{t}", 1, int(t), 0, 0) for t in args.shapes.split(",") if t]
-        variants += [(f"tower128_v{v}", 1, 8, 0, int(v)) for v in args.vars.split(",") if v]
-        for name, mode, shape, abl, var in variants:
+        variants = [("layers", 0, 5, 0), ("tower64", 1, 5, 0), ("tower128", 1, 8, 0), ("tower128_group", 1, 8, 0)]
+        variants += [(f"tower128_abl{a}", 1, 8, int(a)) for a in args.ablations.split(",") if a]
+        variants += [(f"tower_s{t}", 1, int(t), 0) for t in args.shapes.split(",") if t]
+        for name, mode, shape, abl in variants:
             lib.azg_pv_set_tuning(5, mode)
             lib.azg_pv_set_tuning(6, shape)
             lib.azg_pv_set_tuning(8, abl)
-            lib.azg_pv_set_tuning(10, var)
             lib.azg_pv_set_tuning(17, 1 if name.endswith("_group") else 0)   # claim an M tile x all N tiles
             for _ in range(2):
                 eng.forward_into(x, probs, values)
@@ -79,7 +75,6 @@ def main():
     lib.azg_pv_set_tuning(5, 2)
     lib.azg_pv_set_tuning(6, 8)
     lib.azg_pv_set_tuning(8, 0)
-    lib.azg_pv_set_tuning(10, 0)
 
 
 if __name__ == "__main__":

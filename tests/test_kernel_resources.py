@@ -42,7 +42,7 @@ SCRATCH_BUDGET = [
     # chunk loop only (tower claim / epilogue)
     (r"conv_towerILi128ELi128ELi2ELi2ELi4ELi355E", 176),
     (r"conv_towerILi256ELi128ELi2ELi2ELi4ELi355E", 272),
-    (r"conv3x3_haloILi(128|256)ELi64ELi(2|4)ELi1ELi(4|8)ELi[01]ELi0ELi99E", 0),
+    (r"conv3x3_haloILi(128|256)ELi64ELi(2|4)ELi1ELi(4|8)ELi[01]ELi99E", 0),
     (r"conv_towerILi64ELi64E", 0),
     (r"conv_towerILi128ELi128ELi4ELi1ELi16E", 48),
     # train convs at C <= 128 (the 6x128 train step) and the weight grad
