@@ -28,6 +28,7 @@ _SIGS = {
     "azg_mcts_create": (_I32, [ctypes.POINTER(MctsConfig), _I32, ctypes.POINTER(_P)]),
     "azg_mcts_destroy": (_I32, [_P]),
     "azg_mcts_set_root": (_I32, [_P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "azg_mcts_set_budget": (_I32, [_P, _I32, _I32, _I32]),
     "azg_mcts_advance": (_I32, [_P, _P, _P, _P, ctypes.POINTER(_I32), _I32]),
     "azg_mcts_advance_boards": (_I32, [_P, _P, _P, _P, _P, ctypes.POINTER(_I32), _I32]),
     "azg_mcts_feed": (_I32, [_P, _P, _P]),
@@ -111,6 +112,12 @@ class SearchForest:
         caps = getattr(game, "captures", None) or {1: 0, 2: 0}
         _check(self.lib.azg_mcts_set_root(self.h, g, _addr(board), int(game.current_player), lr, lc,
                                           int(caps[1]), int(caps[2]), int(move_number)))
+
+    def set_budget(self, g: int, n_simulations: int = -1, root_noise: int = -1) -> None:
+        """Slot g's simulation budget and whether its root may get Dirichlet noise, from the
+        next set_root on (azg_mcts_set_budget); a negative value means the forest's own
+        n_simulations / add_dirichlet_noise."""
+        _check(self.lib.azg_mcts_set_budget(self.h, g, int(n_simulations), int(root_noise)))
 
     def advance(self) -> int:
         n = _I32(0)

@@ -102,6 +102,8 @@ static void play(int rules, int games, int sims, bool boards_mode, int threads)
                 CHECK(azg_mcts_clear(h, g) == 0);
                 CHECK(azg_mcts_tree_size(h, g) == 0);
             } else {
+                // playout cap: every third move of a game at a small budget without noise
+                CHECK(azg_mcts_set_budget(h, g, moves[g] % 3 == 1 ? 5 : -1, moves[g] % 3 == 1 ? 0 : -1) == 0);
                 CHECK(azg_mcts_set_root(h, g, board[g].data(), player[g], best / 15, best % 15, caps[2 * g],
                                         caps[2 * g + 1], moves[g]) == 0);
             }
@@ -148,6 +150,8 @@ int main()
     CHECK(azg_mcts_get_pi(h, 0, pi) != 0);
     CHECK(azg_mcts_get_pi(h, 5, pi) != 0);
     CHECK(azg_mcts_clear(h, -1) != 0);
+    CHECK(azg_mcts_set_budget(h, 1, 4, 0) != 0 && azg_mcts_set_budget(h, -1, 4, 0) != 0);
+    CHECK(azg_mcts_set_budget(nullptr, 0, 4, 0) != 0 && azg_mcts_set_budget(h, 0, 0, 0) == 0);
     const int32_t twice[2] = {7, 7};
     int32_t cp[4], w[2], o[2];
     CHECK(azg_mcts_replay(0, 15, nullptr, 1, 0, 0, twice, 2, nullptr, cp, w, o) != 0);

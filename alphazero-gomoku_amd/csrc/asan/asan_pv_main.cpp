@@ -123,6 +123,12 @@ int main()
             CHECK(azg_pv_bind_ema(h, nullptr, nullptr, 0.f) == 0 && azg_pv_get_ema(h, nullptr, nullptr, nullptr) == 0);
         }
         CHECK(azg_pv_train_backward(h, &dummy, &dummy, &dummy, 4, &dummy, nullptr) != 0);
+        // the weighted step: the batch and the pointers are checked before the binding, on an unbound handle
+        CHECK(azg_pv_train_backward_weighted(h, &dummy, &dummy, &dummy, &dummy, nullptr, 1, &dummy, nullptr) != 0);
+        CHECK(std::strstr(azg_pv_last_error(), "batch") != nullptr);
+        CHECK(azg_pv_train_backward_weighted(h, &dummy, &dummy, nullptr, nullptr, nullptr, 4, &dummy, nullptr) != 0);
+        CHECK(azg_pv_train_backward_weighted(h, &dummy, &dummy, &dummy, nullptr, nullptr, 4, &dummy, nullptr) != 0);
+        CHECK(std::strstr(azg_pv_last_error(), "not bound") != nullptr);
         CHECK(azg_pv_train_apply(h, &dummy, &dummy, 1, 1e-3f, 0.9f, 0.999f, 1e-8f, 1e-4f, 3.f, nullptr, nullptr) != 0);
         CHECK(azg_pv_destroy(h) == 0);
     }
@@ -141,6 +147,7 @@ int main()
     CHECK(azg_pv_posted(nullptr, 3) == 0);
     CHECK(azg_pv_grad_count(nullptr) == -1);
     CHECK(azg_pv_train_fp32_once(nullptr) != 0);
+    CHECK(azg_pv_train_backward_weighted(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 4, nullptr, nullptr) != 0);
     CHECK(azg_pv_last_seq(nullptr) == 0);
     CHECK(azg_pv_set_eval_precision(nullptr, AZG_PV_EVAL_EXACT) != 0);
     CHECK(azg_pv_get_eval_precision(nullptr) == -1);
@@ -162,6 +169,11 @@ int main()
         CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 5, 8, &id, 1, &f, &f, &f, nullptr) != 0);
         CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 4, 2, 8, &id, 1, &f, &f, &f, nullptr) != 0);
         CHECK(azg_pv_replay_gather(&st, &f, &f, 4, 0, 2, 8, nullptr, 1, &f, &f, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather_weight(nullptr, 4, 0, 2, 8, &id, 1, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather_weight(&f, 4, 0, 2, 8, &id, 1, nullptr, nullptr) != 0);
+        CHECK(azg_pv_replay_gather_weight(&f, 4, 0, 2, 3, &id, 1, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather_weight(&f, 4, 4, 2, 8, &id, 1, &f, nullptr) != 0);
+        CHECK(azg_pv_replay_gather_weight(&f, 4, 0, 5, 8, &id, 0, &f, nullptr) != 0);
     }
     // weighted replay sampling: likewise
     {

@@ -220,6 +220,7 @@ struct GameSearch {
     std::vector<Pending> queue;
     bool final_flush = false;
     int status = AZG_MCTS_IDLE;
+    bool noise_ok = true;   // this move's root may get noise (latched by set_root from the slot's budget)
     // noise hand-off
     bool noise_pending = false;
     int32_t noise_node = -1;
@@ -243,10 +244,17 @@ struct GameSearch {
 
 }  // namespace
 
+// what azg_mcts_set_budget set for a slot; survives azg_mcts_clear
+struct SlotBudget {
+    int32_t sims = -1;    // < 0: cfg.n_simulations
+    int32_t noise = -1;   // < 0: cfg.add_dirichlet_noise
+};
+
 struct azg_mcts {
     azg_mcts_config cfg{};
     int A = 225;
     std::vector<GameSearch> games;
+    std::vector<SlotBudget> budget;
 };
 
 namespace {
@@ -457,6 +465,7 @@ int32_t azg_mcts_create(const azg_mcts_config* cfg, int32_t n_games, azg_mcts** 
     h->cfg = *cfg;
     h->A = cfg->board * cfg->board;
     h->games.resize(n_games);
+    h->budget.resize(n_games);
     *out = h;
     return 0;
 }
@@ -484,7 +493,9 @@ int32_t azg_mcts_set_root(azg_mcts* h, int32_t g, const int8_t* board, int32_t p
     gs.root = s;
     gs.root_key = s.key();
     gs.move_number = move_number;
-    gs.sims_left = h->cfg.n_simulations;
+    const SlotBudget& sb = h->budget[g];
+    gs.sims_left = sb.sims < 0 ? h->cfg.n_simulations : sb.sims;
+    gs.noise_ok = sb.noise < 0 ? h->cfg.add_dirichlet_noise != 0 : sb.noise != 0;
     gs.in_sim = false;
     gs.suspended = false;
     gs.final_flush = false;
@@ -492,6 +503,14 @@ int32_t azg_mcts_set_root(azg_mcts* h, int32_t g, const int8_t* board, int32_t p
     gs.path.clear();
     gs.active = true;
     gs.status = AZG_MCTS_IDLE;
+    return 0;
+}
+
+int32_t azg_mcts_set_budget(azg_mcts* h, int32_t g, int32_t n_simulations, int32_t root_noise)
+{
+    if (!h || g < 0 || g >= (int)h->games.size()) return fail("azg_mcts_set_budget: bad arguments");
+    h->budget[g].sims = n_simulations < 0 ? -1 : n_simulations;
+    h->budget[g].noise = root_noise < 0 ? -1 : (root_noise != 0);
     return 0;
 }
 
@@ -513,11 +532,10 @@ int32_t azg_mcts_feed(azg_mcts* h, const float* probs, const float* values)
 {
     if (!h || !probs || !values) return fail("azg_mcts_feed: null argument");
     const int A = h->A;
-    const bool noise_cfg = h->cfg.add_dirichlet_noise != 0;
     size_t off = 0;
     for (auto& gs : h->games) {
         if (gs.status != AZG_MCTS_NEED_EVAL) continue;
-        const bool noise_move = noise_cfg && gs.move_number < h->cfg.apply_dirichlet_n_first_moves;
+        const bool noise_move = gs.noise_ok && gs.move_number < h->cfg.apply_dirichlet_n_first_moves;
         for (size_t i = 0; i < gs.queue.size(); ++i, ++off) {
             const Pending& pd = gs.queue[i];
             Node& nd = gs.nodes[gs.make_node(pd.key)];

@@ -38,6 +38,21 @@ __global__ __launch_bounds__(256) void replay_gather_kernel(
     if (j == 0) z_out[b] = zs[pos];
 }
 
+// One per-position fp32 value per sample (the policy loss weight): the same id -> slot map,
+// one thread per sample.
+__global__ __launch_bounds__(256) void replay_gather_weight_kernel(
+    const float* __restrict__ vals, int cap_pos, int head, int count, int nsym, const int64_t* __restrict__ ids,
+    int batch, float* __restrict__ out)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= batch) return;
+    const int64_t last = (int64_t)count * nsym - 1;
+    int64_t id = ids[b];
+    id = id < 0 ? 0 : (id > last ? last : id);
+    const int pos = (int)(((int64_t)head + id / nsym) % cap_pos);
+    out[b] = vals[pos];
+}
+
 }  // namespace azg
 
 extern "C" int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, const float* zs, int32_t cap_pos,
@@ -55,5 +70,22 @@ extern "C" int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, 
     hipLaunchKernelGGL(replay_gather_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, stones, pis, zs,
                        cap_pos, head, count, nsym, ids, x, pi_out, z_out);
     if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_gather: launch", e);
+    return 0;
+}
+
+extern "C" int32_t azg_pv_replay_gather_weight(const float* vals, int32_t cap_pos, int32_t head, int32_t count,
+                                               int32_t nsym, const int64_t* ids, int32_t batch, float* out,
+                                               void* stream)
+{
+    using namespace azg;
+    if (!vals || !ids || !out) return set_error("azg_pv_replay_gather_weight: null argument", hipSuccess);
+    if (nsym != 1 && nsym != 8) return set_error("azg_pv_replay_gather_weight: nsym must be 1 or 8", hipSuccess);
+    if (batch < 1) return set_error("azg_pv_replay_gather_weight: batch must be >= 1", hipSuccess);
+    if (cap_pos < 1) return set_error("azg_pv_replay_gather_weight: cap_pos must be >= 1", hipSuccess);
+    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_gather_weight: count outside [1, cap_pos]", hipSuccess);
+    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_gather_weight: head outside [0, cap_pos)", hipSuccess);
+    hipLaunchKernelGGL(replay_gather_weight_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, vals, cap_pos, head, count, nsym, ids, batch, out);
+    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_gather_weight: launch", e);
     return 0;
 }

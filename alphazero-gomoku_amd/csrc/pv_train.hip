@@ -397,6 +397,75 @@ __global__ __launch_bounds__(256) void heads_loss_kernel(
     }
 }
 
+// heads_loss_kernel with per-board loss weights (azg_pv_train_backward_weighted): wp (policy)
+// and wv (value), fp32 [B], either may be null = all ones; the divisor stays B.  A copy of the
+// kernel above -- which stays untouched, so the unweighted step keeps its code object -- with
+// each seed multiplied by its weight LAST: a weight of 1.0 gives the unweighted bits, and a
+// power of two scales every gradient behind the seeds exactly.
+__global__ __launch_bounds__(256) void heads_loss_weighted_kernel(
+    const float* __restrict__ lpre, const float* __restrict__ bpf, const float* __restrict__ hpre,
+    const float* __restrict__ bv1, const float* __restrict__ wv2, const float* __restrict__ bv2,
+    const float* __restrict__ pis, const float* __restrict__ zs, const float* __restrict__ wp,
+    const float* __restrict__ wv, float* __restrict__ dlogits, float* __restrict__ hv, float* __restrict__ dhv,
+    float* __restrict__ dpre, float* __restrict__ lossb, int B, int lps, int hps)
+{
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    float lg[4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lane + 64 * t;
+        lg[t] = j < ACTIONS ? lpre[(size_t)b * lps + j] + bpf[j] : -INFINITY;
+        mx = fmaxf(mx, lg[t]);
+    }
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (lane + 64 * t < ACTIONS) se += expf(lg[t] - mx);
+    se = wave_sum(se);
+    const float lse = logf(se);
+    const float* tp = pis + (size_t)b * ACTIONS;
+    float kl = 0.f, st = 0.f, tv[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lane + 64 * t;
+        tv[t] = j < ACTIONS ? tp[j] : 0.f;
+        if (j < ACTIONS) {
+            const float lp = (lg[t] - mx) - lse;
+            if (tv[t] > 0.f) kl += tv[t] * (logf(tv[t]) - lp);
+            st += tv[t];
+        }
+    }
+    kl = wave_sum(kl);
+    st = wave_sum(st);
+    const float invB = 1.f / (float)B;
+    const float wpb = wp ? wp[b] : 1.f, wvb = wv ? wv[b] : 1.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int j = lane + 64 * t;
+        if (j < ACTIONS) {
+            const float lp = (lg[t] - mx) - lse;
+            dlogits[(size_t)b * ACTIONS + j] = ((expf(lp) * st - tv[t]) * invB) * wpb;
+        }
+    }
+    const float hid = fmaxf(hpre[(size_t)b * hps + lane] + bv1[lane], 0.f);
+    const float pre = wave_sum(wv2[lane] * hid) + bv2[0];
+    const float v = tanhf(pre);
+    const float z = zs[b];
+    const float dv = 2.f * (v - z) / (float)B;
+    const float dp = (dv * (1.f - v * v)) * wvb;
+    hv[(size_t)b * VHID + lane] = hid;
+    dhv[(size_t)b * VHID + lane] = hid > 0.f ? dp * wv2[lane] : 0.f;
+    if (lane == 0) {
+        lossb[b * 2 + 0] = wpb * kl;
+        lossb[b * 2 + 1] = wvb * ((v - z) * (v - z));
+        dpre[b] = dp;
+    }
+}
+
 // bias / value_fc2 gradients and the loss means: one wave per output (fixed order)
 constexpr int HSG_OUT = ACTIONS + VHID + VHID + 2;
 __global__ __launch_bounds__(256) void heads_small_grads_kernel(
@@ -780,8 +849,11 @@ static inline int grid_for(int64_t total) { int64_t b = (total + 255) / 256; ret
         if (_e != hipSuccess) return set_error(what, _e); \
     } while (0)
 
+// per-board loss weights of one step (device fp32 [B]); null = all ones
+struct LossWeights { const float* wp = nullptr; const float* wv = nullptr; };
+
 template <int C>
-static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, const float* zs, int B,
+static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, const float* zs, LossWeights lw, int B,
                                 float* losses, hipStream_t st)
 {
     TrainWS* w = ws_of(h);
@@ -1015,10 +1087,16 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
         AZG_CK(launch_head_proj_partials(C, last_apply, hs, st), "train: head_proj_partials");
         AZG_CK(launch_head_bn_apply_feat(w->fp, w->fv, w->feat, B, hs, st), "train: head_bn_apply_feat");
         AZG_CK(launch_heads_fc(w->feat, h->wfc, w->pre, B, st), "train: heads_fc");
-        hipLaunchKernelGGL(heads_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w->pre, P + h->poff[h->t_pfc_b],
-                           w->pre + ACTIONS, P + h->poff[h->t_vfc1_b], P + h->poff[h->t_vfc2_w],
-                           P + h->poff[h->t_vfc2_b], pis, zs, w->dlogits, w->hv, w->dhv, w->dpre, w->lossb, B,
-                           FC_OUT, FC_OUT);
+        if (lw.wp || lw.wv)
+            hipLaunchKernelGGL(heads_loss_weighted_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w->pre,
+                               P + h->poff[h->t_pfc_b], w->pre + ACTIONS, P + h->poff[h->t_vfc1_b],
+                               P + h->poff[h->t_vfc2_w], P + h->poff[h->t_vfc2_b], pis, zs, lw.wp, lw.wv, w->dlogits,
+                               w->hv, w->dhv, w->dpre, w->lossb, B, FC_OUT, FC_OUT);
+        else
+            hipLaunchKernelGGL(heads_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w->pre, P + h->poff[h->t_pfc_b],
+                               w->pre + ACTIONS, P + h->poff[h->t_vfc1_b], P + h->poff[h->t_vfc2_w],
+                               P + h->poff[h->t_vfc2_b], pis, zs, w->dlogits, w->hv, w->dhv, w->dpre, w->lossb, B,
+                               FC_OUT, FC_OUT);
         AZG_CK(hipGetLastError(), "train: heads_loss");
         HeadDgradArgs hd{};
         hd.dlogits = w->dlogits;
@@ -1160,8 +1238,8 @@ static int32_t train_backward_t(azg_pv* h, const float* x, const float* pis, con
     return 0;
 }
 
-int32_t train_backward(azg_pv* h, const float* x, const float* pis, const float* zs, int B, float* losses,
-                       hipStream_t st)
+int32_t train_backward(azg_pv* h, const float* x, const float* pis, const float* zs, LossWeights lw, int B,
+                       float* losses, hipStream_t st)
 {
     // a split-count override (key 27) above what the slabs were sized for: re-allocate
     if (TrainWS* w0 = ws_of(h); w0 && wgrad_splits(h->C, B * PIX) > w0->slab_S) free_train_workspace(h);
@@ -1202,9 +1280,9 @@ int32_t train_backward(azg_pv* h, const float* x, const float* pis, const float*
     const int C = h->C;
     int32_t r;
     switch (C) {
-        case 64: r = train_backward_t<64>(h, x, pis, zs, B, losses, st); break;
-        case 128: r = train_backward_t<128>(h, x, pis, zs, B, losses, st); break;
-        case 256: r = train_backward_t<256>(h, x, pis, zs, B, losses, st); break;
+        case 64: r = train_backward_t<64>(h, x, pis, zs, lw, B, losses, st); break;
+        case 128: r = train_backward_t<128>(h, x, pis, zs, lw, B, losses, st); break;
+        case 256: r = train_backward_t<256>(h, x, pis, zs, lw, B, losses, st); break;
         default: r = set_error("train: bad channels", hipErrorInvalidValue); break;
     }
     h->train_fp32_once = false;
@@ -1305,7 +1383,18 @@ extern "C" int32_t azg_pv_train_backward(azg_pv* h, const float* x, const float*
     if (!h || !h->params || !h->grads) return azg::set_error("azg_pv_train_backward: handle not bound with grads", hipSuccess);
     if (!x || !pis || !zs || !losses) return azg::set_error("azg_pv_train_backward: null argument", hipSuccess);
     if (batch < 2) return azg::set_error("azg_pv_train_backward: batch must be >= 2 (train-mode BatchNorm)", hipSuccess);
-    return azg::train_backward(h, x, pis, zs, batch, losses, (hipStream_t)stream);
+    return azg::train_backward(h, x, pis, zs, azg::LossWeights{}, batch, losses, (hipStream_t)stream);
+}
+
+extern "C" int32_t azg_pv_train_backward_weighted(azg_pv* h, const float* x, const float* pis, const float* zs,
+                                                  const float* wp, const float* wv, int32_t batch, float* losses,
+                                                  void* stream)
+{
+    if (!h) return azg::set_error("azg_pv_train_backward_weighted: null handle", hipSuccess);
+    if (batch < 2) return azg::set_error("azg_pv_train_backward_weighted: batch must be >= 2 (train-mode BatchNorm)", hipSuccess);
+    if (!x || !pis || !zs || !losses) return azg::set_error("azg_pv_train_backward_weighted: null argument", hipSuccess);
+    if (!h->params || !h->grads) return azg::set_error("azg_pv_train_backward_weighted: handle not bound with grads", hipSuccess);
+    return azg::train_backward(h, x, pis, zs, azg::LossWeights{wp, wv}, batch, losses, (hipStream_t)stream);
 }
 
 extern "C" int32_t azg_pv_train_apply(azg_pv* h, float* exp_avg, float* exp_avg_sq, int64_t step, float lr,

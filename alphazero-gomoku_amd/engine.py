@@ -345,10 +345,39 @@ class PolicyValueEngine:
                                                  1 if mean8 else 0, int(boards.shape[0]), ptr(probs), ptr(values),
                                                  ptr(priors), _stream(self.device)), self.lib)
 
-    def train_backward(self, x, pis, zs, losses):
+    def loss_weight(self, w, batch: int, name: str = "weight"):
+        """A per-example loss weight as the device tensor train_backward takes: None stays
+        None; a device tensor must be contiguous float32 [B] or [B,1] on this engine's device
+        -- its VALUES are not checked (that would need a host sync): the caller passes finite
+        weights >= 0; anything else is taken as a host array, which is checked (length,
+        finite, >= 0) and copied over."""
+        if w is None:
+            return None
+        if torch.is_tensor(w) and w.device.type == "cuda":
+            if w.dtype != torch.float32 or tuple(w.shape) not in ((batch,), (batch, 1)) or not w.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape [{batch}] or [{batch}, 1], "
+                                 f"got {w.dtype} {tuple(w.shape)}")
+            if self.device.index is not None and w.device != self.device:
+                raise ValueError(f"{name} is on {w.device}, the engine on {self.device}")
+            return w
+        a = np.asarray(w.numpy() if torch.is_tensor(w) else w, dtype=np.float32)
+        if a.shape not in ((batch,), (batch, 1)):
+            raise ValueError(f"{name} must have shape [{batch}] or [{batch}, 1], got {a.shape}")
+        if not np.isfinite(a).all() or (a < 0).any():
+            raise ValueError(f"{name} must be finite and >= 0")
+        return torch.from_numpy(np.ascontiguousarray(a.reshape(-1))).to(self.device)
+
+    def train_backward(self, x, pis, zs, losses, policy_weight=None, value_weight=None):
+        """One azg_pv_train_backward; with a weight (device float32 [B], see loss_weight) the
+        weighted entry point: policy_loss = mean(wp KL), value_loss = mean(wv (v - z)^2)."""
         self.sync_dirty()
-        check(self.lib.azg_pv_train_backward(self.h, ptr(x), ptr(pis), ptr(zs), int(x.shape[0]), ptr(losses),
-                                             _stream(self.device)), self.lib)
+        if policy_weight is None and value_weight is None:
+            check(self.lib.azg_pv_train_backward(self.h, ptr(x), ptr(pis), ptr(zs), int(x.shape[0]), ptr(losses),
+                                                 _stream(self.device)), self.lib)
+        else:
+            check(self.lib.azg_pv_train_backward_weighted(self.h, ptr(x), ptr(pis), ptr(zs), ptr(policy_weight),
+                                                          ptr(value_weight), int(x.shape[0]), ptr(losses),
+                                                          _stream(self.device)), self.lib)
         self._seen = self._versions()
         self.reattach_grads()
 

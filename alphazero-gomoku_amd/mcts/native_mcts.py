@@ -132,14 +132,32 @@ class NativeSelfPlay:
         the GPU evaluates another (leaves cross PCIe as int8 boards, encoded on the GPU).
     Every game draws from its own RandomState, so results are identical in both modes
     and for any grouping.  Statistics: boards, forwards, nn_seconds (host time waiting
-    for / inside evaluation), search_seconds, max_batch."""
+    for / inside evaluation), search_seconds, max_batch.
+
+    ``playout_cap=(p_full, fast_sims)`` turns on KataGo's playout cap randomization: before
+    each move a game flips a coin from a stream of its own, RandomState((seed + 0x9E3779B1)
+    % 2**32), one draw per move -- its main RandomState (noise, move sampling) is not
+    touched, so a game's coins follow from its seed alone.  With probability p_full the move
+    is searched at n_simulations with noise as configured, else at fast_sims without root
+    noise.  Moves are chosen the same way for both kinds and the tree is reused.  Examples
+    become 4-tuples (state, pi, z, policy_weight): 1.0 after a full search, 0.0 after a fast
+    one (all 8 images alike); ``full_moves`` / ``fast_moves`` count them."""
+
+    COIN_SALT = 0x9E3779B1
 
     def __init__(self, evaluate: Optional[Callable], game_class, n_games: int, n_simulations: int,
                  cpuct: float = 1.0, batch_size: int = 32, dirichlet_alpha: float = 0.03, epsilon: float = 0.03,
                  apply_dirichlet_n_first_moves: int = 10, add_dirichlet_noise: bool = True, n_threads: int = 0,
-                 evaluator_factory: Optional[Callable] = None, groups: int = 2):
+                 evaluator_factory: Optional[Callable] = None, groups: int = 2, playout_cap=None):
         if (evaluate is None) == (evaluator_factory is None):
             raise ValueError("give exactly one of evaluate / evaluator_factory")
+        if playout_cap is not None:
+            p_full, fast_sims = playout_cap
+            if not 0.0 <= float(p_full) <= 1.0 or int(fast_sims) != fast_sims or int(fast_sims) < 0:
+                raise ValueError(f"playout_cap must be (p_full in [0, 1], fast_sims >= 0), got {playout_cap!r}")
+            playout_cap = (float(p_full), int(fast_sims))
+        self.playout_cap = playout_cap
+        self.full_moves = self.fast_moves = 0
         self.game_class = game_class
         self.n_games = n_games
         self.alpha, self.eps = dirichlet_alpha, epsilon
@@ -176,6 +194,9 @@ class NativeSelfPlay:
         if seeds is None:
             seeds = np.random.randint(0, 2 ** 31 - 1, size=G)
         rngs = [np.random.RandomState(int(s)) for s in seeds]
+        coins = None
+        if self.playout_cap is not None:
+            coins = [np.random.RandomState((int(s) + self.COIN_SALT) % 2 ** 32) for s in seeds]
         if games is None:
             games = []
             for _ in range(G):
@@ -183,6 +204,7 @@ class NativeSelfPlay:
                 g.current_player = 1
                 games.append(g)
         hist: List[list] = [[] for _ in range(G)]
+        full = [True] * G        # the move being searched is a full one (playout cap)
         moves = [0] * G
         results = [None] * G
         live = [0] * len(self.forests)
@@ -190,7 +212,7 @@ class NativeSelfPlay:
             f = self.forests[k]
             for g in range(lo, hi):
                 f.clear(g - lo)          # a fresh tree per game, reused across its moves
-                f.set_root(g - lo, games[g], len(games[g].move_history))
+                self._start_move(f, g - lo, g, games[g], coins, full)
             live[k] = hi - lo
         pending = [False] * len(self.forests)
         while any(live) or any(pending):
@@ -234,15 +256,29 @@ class NativeSelfPlay:
                         self.forwards += 1
                         self.max_batch = max(self.max_batch, n)
                     self._play_done(f, done, lo, games, hist, moves, results, live, k, rngs, temp_fn, max_moves,
-                                    use_symmetries)
+                                    use_symmetries, coins, full)
                     if pending[k] or not live[k] or not len(done):
                         break
                 self.search_seconds += time.perf_counter() - t0
         self.rounds = max(self.rounds, max(moves) if moves else 0)
         return results
 
+    def _start_move(self, f, i, g, game, coins, full):
+        """Start the search of game g's next move (slot i of forest f), under the playout cap
+        with the budget its coin decides."""
+        if coins is not None:
+            p_full, fast_sims = self.playout_cap
+            full[g] = bool(coins[g].random_sample() < p_full)
+            if full[g]:
+                f.set_budget(i, -1, -1)
+                self.full_moves += 1
+            else:
+                f.set_budget(i, fast_sims, 0)
+                self.fast_moves += 1
+        f.set_root(i, game, len(game.move_history))
+
     def _play_done(self, f, done, lo, games, hist, moves, results, live, k, rngs, temp_fn, max_moves,
-                   use_symmetries):
+                   use_symmetries, coins=None, full=None):
         """Games whose move search finished: sample (per-game RNG), play, restart."""
         from selfplay import sample_action_from_pi
         for i in done:
@@ -254,7 +290,10 @@ class NativeSelfPlay:
             action = sample_action_from_pi(pi, temp_fn(moves[g]), rngs[g])
             if game.get_valid_moves()[action] != 1.0:
                 action = int(np.argmax(pi))
-            hist[g].append((state_enc, pi.copy(), int(game.current_player)))
+            if coins is None:
+                hist[g].append((state_enc, pi.copy(), int(game.current_player)))
+            else:
+                hist[g].append((state_enc, pi.copy(), int(game.current_player), 1.0 if full[g] else 0.0))
             game.do_move(divmod(action, game.size))
             moves[g] += 1
             self.moves += 1
@@ -263,7 +302,7 @@ class NativeSelfPlay:
                 self.game_lengths.append(moves[g])
                 live[k] -= 1
             else:
-                f.set_root(i, game, len(game.move_history))
+                self._start_move(f, i, g, game, coins, full)
 
     @staticmethod
     def _finish(history, winner, use_symmetries):
@@ -274,12 +313,15 @@ class NativeSelfPlay:
         when many games ended in one round); the values are the same permutations."""
         if not history:
             return [], winner
-        zs = [0.0 if winner == 0 else (1.0 if winner == who else -1.0) for _, _, who in history]
+        zs = [0.0 if winner == 0 else (1.0 if winner == h[2] else -1.0) for h in history]
+        # under a playout cap every example carries its position's policy weight as a 4th field
+        weigh = (lambda out, k: out) if len(history[0]) == 3 else \
+            (lambda out, k: [e + (history[i // k][3],) for i, e in enumerate(out)])
         S = np.stack([h[0] for h in history]).astype(np.float32)          # [T, C, n, n]
         n = S.shape[2]
         P = np.stack([h[1] for h in history]).astype(np.float32).reshape(len(history), n, n)
         if not use_symmetries:
-            return [(S[t], P[t].reshape(-1), zs[t]) for t in range(len(history))], winner
+            return weigh([(S[t], P[t].reshape(-1), zs[t]) for t in range(len(history))], 1), winner
         imgs = []
         for k in range(4):
             s_k = np.rot90(S, k, axes=(2, 3))
@@ -288,7 +330,7 @@ class NativeSelfPlay:
             imgs.append((np.ascontiguousarray(np.flip(s_k, axis=3)),
                          np.ascontiguousarray(np.flip(p_k, axis=2)).reshape(len(history), -1)))
         out = [(si[t], pi[t], zs[t]) for t in range(len(history)) for si, pi in imgs]
-        return out, winner
+        return weigh(out, 8), winner
 
 
 class NativeEval:

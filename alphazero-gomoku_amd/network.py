@@ -560,21 +560,34 @@ class PyTorchModel:
 
     # ---------------- training ----------------
     def train_batch(self, states: np.ndarray, target_pis: np.ndarray, target_vs: np.ndarray,
-                    epochs: int = 1) -> dict:
+                    epochs: int = 1, policy_weight=None, value_weight=None) -> dict:
         """network.py:199-235: per epoch zero_grad, train-mode forward, KLDiv(batchmean)
-        + MSE, backward, clip_grad_norm_(3.0), Adam step.  Leaves the net in train mode."""
+        + MSE, backward, clip_grad_norm_(3.0), Adam step.  Leaves the net in train mode.
+
+        policy_weight / value_weight (optional host arrays [B] or [B,1], finite, >= 0):
+        per-example loss weights, policy_loss = mean_b(wp_b KL_b) and value_loss =
+        mean_b(wv_b (v_b - z_b)^2) -- the divisor stays B.  A weight of 0 takes an example
+        out of that head's loss; it still passes through the forward and BatchNorm."""
         self.net.train()
         dev = self.engine.device
+        B = len(states)
+        policy_weight = self.engine.loss_weight(policy_weight, B, "policy_weight")
+        value_weight = self.engine.loss_weight(value_weight, B, "value_weight")
         s = torch.from_numpy(np.ascontiguousarray(states, dtype=np.float32)).to(dev)
         t = torch.from_numpy(np.ascontiguousarray(target_pis, dtype=np.float32)).to(dev)
         z = torch.from_numpy(np.ascontiguousarray(target_vs, dtype=np.float32).reshape(-1, 1)).to(dev)
-        return self.train_batch_device(s, t, z, epochs)
+        return self.train_batch_device(s, t, z, epochs, policy_weight=policy_weight, value_weight=value_weight)
 
     def train_batch_device(self, s: torch.Tensor, t: torch.Tensor, z: torch.Tensor, epochs: int = 1,
-                           return_tensor: bool = False):
+                           return_tensor: bool = False, policy_weight=None, value_weight=None):
         """train_batch on device-resident tensors.  return_tensor=True returns the
         mean losses as a float32 [3] device tensor (policy, value, total) without a
         host sync, so consecutive steps pipeline on the stream.
+
+        policy_weight / value_weight: train_batch's loss weights as contiguous float32
+        device tensors [B] or [B,1].  Their dtype, shape and device are checked; their
+        VALUES are not -- that would need a host sync -- so the caller passes finite
+        weights >= 0.  (Host arrays are accepted too and are checked in full.)
 
         A step whose split-fp16 forward (tuning key 49) met an activation beyond fp16's
         range on any rank does not commit on the device (include/azg_pv.h
@@ -588,12 +601,15 @@ class PyTorchModel:
         self.net.train()
         eng = self.engine
         self._settle_skips()
+        B = int(s.shape[0])
+        wp = eng.loss_weight(policy_weight, B, "policy_weight")
+        wv = eng.loss_weight(value_weight, B, "value_weight")
         losses = torch.empty(3, dtype=torch.float32, device=eng.device)
         acc = None
         vals = None
         for _ in range(epochs):
             step0 = self.optimizer.get_step()
-            self._one_step(s, t, z, losses)
+            self._one_step(s, t, z, losses, wp, wv)
             if not return_tensor:
                 # one host sync per step (the reference reads its losses per step too)
                 v = torch.cat((losses, eng.flat_grads_ext[-1:])).double().tolist()
@@ -603,7 +619,7 @@ class PyTorchModel:
                     eng.train_recoveries += 1
                     self._skips_seen += 1
                     eng.train_fp32_once()
-                    self._one_step(s, t, z, losses)
+                    self._one_step(s, t, z, losses, wp, wv)
                     v = losses.double().tolist()
                 vals = v[:3] if vals is None else [a + b for a, b in zip(vals, v[:3])]
             elif epochs > 1:
@@ -613,9 +629,9 @@ class PyTorchModel:
         vals = [a / float(epochs) for a in vals]
         return {"policy_loss": vals[0], "value_loss": vals[1], "total_loss": vals[2]}
 
-    def _one_step(self, s, t, z, losses):
+    def _one_step(self, s, t, z, losses, wp=None, wv=None):
         eng = self.engine
-        eng.train_backward(s, t, z, losses)
+        eng.train_backward(s, t, z, losses, wp, wv)
         if self.grad_hook is not None:
             self.grad_hook(eng.flat_grads_ext)   # the gradients AND the step's skip word
         self.optimizer.hip_step(self.max_grad_norm)

@@ -22,6 +22,13 @@ it on the device (csrc/pv_replay_weights.hip): weights are integers, 2**16 quant
 of weight, so their running sums are exact and the draw is an integer function of the
 random words -- tests/replay_weights_reference.py reproduces every id in Python integers.
 A buffer that never sees a weighted call allocates and does nothing new.
+
+Also opt-in, and independent of the sampling weight: one POLICY LOSS WEIGHT per position
+(``add_positions(..., policy_weight=...)``, ``set_policy_weights``), fp32, which
+``sample(..., with_policy_weight=True)`` gathers for the batch on the device
+(azg_pv_replay_gather_weight) for ``train_batch_device(policy_weight=...)`` -- playout cap
+randomization stores 0.0 for positions searched at the small budget.  It does not exist
+until the first call that passes weights; ``to_host`` and the pickle never carry it.
 """
 from __future__ import annotations
 
@@ -90,12 +97,14 @@ class DeviceReplayBuffer:
         self._wq = None            # the same memory as int32 (quanta < 2**31), for torch's copies and fills
         self._prefix = None        # [cap_pos] running sums of the weights in ring order (uint64 bits in int64)
         self._prefix_ok = False    # False whenever the weights or the ring have moved since the last scan
+        # policy loss weights: [cap_pos] float32 by slot, nothing until the first call that passes them
+        self._pw = None
 
     def __len__(self) -> int:
         return self.count * self.nsym
 
     # ---------------------------------------------------------------- writing
-    def add_positions(self, examples, surprise=None, mix: float = 0.5) -> None:
+    def add_positions(self, examples, surprise=None, mix: float = 0.5, policy_weight=None) -> None:
         """Canonical (state [3,15,15], pi [225], z) tuples, as
         selfplay_games(use_symmetries=False) returns them; the oldest positions are
         overwritten (= the deque's eviction of whole groups of nsym images).
@@ -105,12 +114,23 @@ class DeviceReplayBuffer:
         positions the weights  (1 - mix) + mix * n * s_i / sum(s)  (azg_pv_replay_surprise_weights:
         non-finite and non-positive surprises count as 0; all of them 0: every weight 1), in
         quanta of 2**-16; the sum runs over all n examples passed even where only the newest
-        cap_pos survive.  Without it the new positions weigh 1.0 once the buffer has weights."""
+        cap_pos survive.  Without it the new positions weigh 1.0 once the buffer has weights.
+
+        policy_weight (optional host float array [n], finite, >= 0): the positions' policy
+        loss weights (sample(with_policy_weight=True)).  Without it the new positions count
+        1.0 once the buffer has policy weights.  Examples may be 4-tuples (playout-cap
+        self-play); their 4th field is NOT read here -- pass it as policy_weight."""
         examples = list(examples)
         if not examples:
             return
         S, P, Z = _stack(examples)
         n_all = len(S)
+        if policy_weight is not None:
+            policy_weight = np.asarray(policy_weight, dtype=np.float32).reshape(-1)
+            if len(policy_weight) != n_all:
+                raise ValueError(f"{len(policy_weight)} policy weights for {n_all} examples")
+            if not np.isfinite(policy_weight).all() or (policy_weight < 0).any():
+                raise ValueError("policy_weight must be finite and >= 0")
         if surprise is not None:
             if not 0.0 <= float(mix) <= 1.0:
                 raise ValueError(f"mix must be in [0, 1], got {mix!r}")
@@ -130,6 +150,8 @@ class DeviceReplayBuffer:
         stones = (p0 + 2 * p1).astype(np.int8).reshape(len(S), _PIX)
         if len(S) > self.cap_pos:     # only the newest cap_pos survive, as in the deque
             stones, P, Z = stones[-self.cap_pos:], P[-self.cap_pos:], Z[-self.cap_pos:]
+            if policy_weight is not None:
+                policy_weight = policy_weight[-self.cap_pos:]
         n = len(stones)
         # one pinned staging buffer [pis | zs | stones]; torch's host allocator keeps the
         # block alive until the copies queued from it have run
@@ -157,6 +179,16 @@ class DeviceReplayBuffer:
         elif self._wq is not None:     # eviction takes the old weights with the old positions
             self._wq[tail:tail + first].fill_(QUANTA)
             self._wq[0:n - first].fill_(QUANTA)
+        if policy_weight is not None:
+            self._ensure_policy_weights()
+            h_pw = torch.empty(n, dtype=torch.float32, pin_memory=True)
+            h_pw.numpy()[...] = policy_weight
+            for lo, hi, at in ((0, first, tail), (first, n, 0)):
+                if hi > lo:
+                    self._pw[at:at + hi - lo].copy_(h_pw[lo:hi], non_blocking=True)
+        elif self._pw is not None:     # eviction takes the old weights with the old positions
+            self._pw[tail:tail + first].fill_(1.0)
+            self._pw[0:n - first].fill_(1.0)
         self._prefix_ok = False
         over = self.count + n - self.cap_pos
         if over > 0:
@@ -204,13 +236,52 @@ class DeviceReplayBuffer:
         w = self.get_weights()
         return float(w.sum() ** 2 / (w * w).sum()) if len(w) and w.any() else 0.0
 
+    # ----------------------------------------------------- policy loss weights
+    def _ensure_policy_weights(self) -> None:
+        if self._pw is None:   # every position held so far counts 1.0
+            self._pw = torch.ones(self.cap_pos, dtype=torch.float32, device=self.device)
+
+    def set_policy_weights(self, w) -> None:
+        """Policy loss weights of the positions held, a host float array [count] in ring
+        order (oldest first): finite, >= 0."""
+        w = np.asarray(w, dtype=np.float32).reshape(-1)
+        if len(w) != self.count or self.count < 1:
+            raise ValueError(f"{len(w)} policy weights for {self.count} positions")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("policy weights must be finite and >= 0")
+        self._ensure_policy_weights()
+        stage = torch.empty(self.count, dtype=torch.float32, pin_memory=True)
+        stage.numpy()[...] = w
+        first = min(self.count, self.cap_pos - self.head)
+        self._pw[self.head:self.head + first].copy_(stage[:first], non_blocking=True)
+        self._pw[0:self.count - first].copy_(stage[first:], non_blocking=True)
+
+    def get_policy_weights(self) -> np.ndarray:
+        """The policy loss weights of the positions held, float32 [count] in ring order (all
+        1.0 for a buffer without them).  Synchronises."""
+        if self._pw is None:
+            return np.ones(self.count, dtype=np.float32)
+        order = (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
+        return self._pw[order].cpu().numpy()
+
+    def _gather_policy_weight(self, d_ids, batch_size: int, st) -> torch.Tensor:
+        """[B] float32: the policy weight of each image id's position, on the device (ones,
+        without a launch or an allocation of the ring's array, for a buffer without them)."""
+        if self._pw is None:
+            return torch.ones(batch_size, dtype=torch.float32, device=self.device)
+        w = torch.empty(batch_size, dtype=torch.float32, device=self.device)
+        check(self.lib.azg_pv_replay_gather_weight(ptr(self._pw), self.cap_pos, self.head, self.count, self.nsym,
+                                                   ptr(d_ids), batch_size, ptr(w), st), self.lib)
+        return w
+
     # --------------------------------------------------------------- sampling
     def draw_ids(self, batch_size: int) -> list:
         """The indices a seeded random.sample(deque, batch_size) picks on the host buffer."""
         return random.sample(range(len(self)), batch_size)
 
-    def sample(self, batch_size: int, ids=None):
-        """Device tensors (s [B,3,15,15], p [B,225], z [B,1]); no host sync."""
+    def sample(self, batch_size: int, ids=None, with_policy_weight: bool = False):
+        """Device tensors (s [B,3,15,15], p [B,225], z [B,1]); no host sync.
+        with_policy_weight: a fourth tensor [B], the positions' policy loss weights."""
         ids = np.asarray(self.draw_ids(batch_size) if ids is None else ids, dtype=np.int64).reshape(-1)
         if len(ids) != batch_size or batch_size < 1:
             raise ValueError(f"{len(ids)} ids for a batch of {batch_size}")
@@ -228,6 +299,9 @@ class DeviceReplayBuffer:
                                                 self.head, self.count, self.nsym, ptr(d_ids), batch_size,
                                                 ptr(s), ptr(p), ptr(z),
                                                 torch.cuda.current_stream(dev).cuda_stream), self.lib)
+            if with_policy_weight:
+                return s, p, z, self._gather_policy_weight(d_ids, batch_size,
+                                                           torch.cuda.current_stream(dev).cuda_stream)
         return s, p, z
 
     def draw_words(self, batch_size: int) -> np.ndarray:
@@ -236,13 +310,14 @@ class DeviceReplayBuffer:
         as it governs draw_ids."""
         return np.array([random.getrandbits(64) for _ in range(2 * batch_size)], dtype=np.uint64).reshape(batch_size, 2)
 
-    def sample_weighted(self, batch_size: int, rnd=None):
+    def sample_weighted(self, batch_size: int, rnd=None, with_policy_weight: bool = False):
         """``sample``'s tensors for a batch drawn WITH replacement, each position in proportion
         to its weight and, with nsym = 8, one of its 8 images uniformly; no host sync and no
         host copy of the weights.  rnd (optional uint64 [batch, 2]): word 0 of an element
         picks the position (azg_pv_replay_draw), the low 3 bits of word 1 the image.  A
         buffer without weights draws as if every weight were 1.0 (and has weights from then
-        on).  The running sums are scanned again only after the weights or the ring moved."""
+        on).  The running sums are scanned again only after the weights or the ring moved.
+        with_policy_weight: a fourth tensor [B], the positions' policy loss weights."""
         if batch_size < 1 or self.count < 1:
             raise ValueError(f"a batch of {batch_size} from {self.count} positions")
         rnd = self.draw_words(batch_size) if rnd is None else np.asarray(rnd)
@@ -268,6 +343,8 @@ class DeviceReplayBuffer:
             check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(self.pis), ptr(self.zs), self.cap_pos,
                                                 self.head, self.count, self.nsym, ptr(d_ids), batch_size,
                                                 ptr(s), ptr(p), ptr(z), st), self.lib)
+            if with_policy_weight:
+                return s, p, z, self._gather_policy_weight(d_ids, batch_size, st)
         return s, p, z
 
     # ------------------------------------------------------------ host format

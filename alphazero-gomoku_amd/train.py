@@ -208,6 +208,7 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     selfplay_precision: Optional[str] = None, score_new_games: bool = False,
                     score_max_examples: int = 4096, history: Optional[list] = None,
                     ema_decay: Optional[float] = None, surprise_weight: Optional[float] = None,
+                    playout_cap_prob: Optional[float] = None, playout_cap_fast_sims: Optional[int] = None,
                     **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
@@ -254,11 +255,41 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     (DeviceReplayBuffer.add_positions(surprise=..., mix=...)); batches are then drawn in
     proportion to the weights on the device (sample_weighted: with replacement, governed by
     random.seed).  Old positions keep the weight they entered with.  The loss is not
-    reweighted.  history entries carry "surprise_weight" and "buffer_ess" (the buffer's
+    reweighted by it (see playout_cap_prob for per-example loss weights).  history entries carry "surprise_weight" and "buffer_ess" (the buffer's
     effective sample size in positions, None when off), and the weights are kept beside the
     buffer pickle in replay_weights_latest{suffix}.npy, applied on start when they match the
     loaded buffer's position count (otherwise every loaded position weighs 1.0).  None, the
-    default, makes none of these calls: the loop samples uniformly as before."""
+    default, makes none of these calls: the loop samples uniformly as before.
+
+    playout_cap_prob / playout_cap_fast_sims (both or neither; needs device_buffer=True, as
+    the host deque and the reference pickle have no place for a weight): KataGo's playout cap
+    randomization.  Each self-play move is searched at n_simulations with probability
+    playout_cap_prob, else at playout_cap_fast_sims without root noise
+    (NativeSelfPlay(playout_cap=...)).  Every position trains the value head; only fully
+    searched ones train the policy head: positions enter the buffer with a policy loss
+    weight of 1.0 or 0.0 (add_positions(policy_weight=...)), batches come with it
+    (sample(with_policy_weight=True)) and the step weighs each example's policy loss by it
+    (train_batch_device(policy_weight=...); the divisor stays the batch size).  The weights
+    are kept beside the buffer pickle in replay_policy_weights_latest{suffix}.npy and
+    restored on start when their length matches the loaded buffer (otherwise every loaded
+    position counts 1.0).  history entries carry "playout_cap": None when off, else
+    {"p_full", "fast_sims", "full_moves", "fast_moves"} of this rank's self-play.  With
+    surprise_weight also on, the surprise of fast positions is set to 0 before they enter
+    the buffer -- their policy target is not trusted, so they get the uniform share only.
+    score_new_games is unchanged: its policy metrics then include the fast positions.
+    None, the default, makes none of these calls."""
+    if (playout_cap_prob is None) != (playout_cap_fast_sims is None):
+        raise ValueError("playout_cap_prob and playout_cap_fast_sims must be given together")
+    playout_cap = None
+    if playout_cap_prob is not None:
+        if isinstance(playout_cap_prob, bool) or not 0.0 <= float(playout_cap_prob) <= 1.0:
+            raise ValueError(f"playout_cap_prob must be in [0, 1], got {playout_cap_prob!r}")
+        if isinstance(playout_cap_fast_sims, bool) or int(playout_cap_fast_sims) != playout_cap_fast_sims \
+                or playout_cap_fast_sims < 0:
+            raise ValueError(f"playout_cap_fast_sims must be an integer >= 0, got {playout_cap_fast_sims!r}")
+        if not device_buffer:
+            raise ValueError("playout_cap_prob needs device_buffer=True (the host ReplayBuffer carries no weights)")
+        playout_cap = (float(playout_cap_prob), int(playout_cap_fast_sims))
     if surprise_weight is not None:
         if isinstance(surprise_weight, bool) or not isinstance(surprise_weight, (int, float, np.floating, np.integer)) \
                 or not 0.0 <= float(surprise_weight) <= 1.0:
@@ -301,6 +332,11 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         saved = np.load(weights_path, allow_pickle=False)
         if saved.shape == (buffer.count,):   # the sidecar of another buffer: start from 1.0 instead
             buffer.set_weights(saved)
+    pweights_path = os.path.join(model_dir, f"replay_policy_weights_latest{suffix}.npy")
+    if playout_cap is not None and buffer.count and os.path.exists(pweights_path):
+        saved = np.load(pweights_path, allow_pickle=False)
+        if saved.shape == (buffer.count,):   # the sidecar of another buffer: start from 1.0 instead
+            buffer.set_policy_weights(saved)
     # a device buffer of single images (nsym = 1: a loaded buffer that is not whole groups
     # of 8) takes the expanded examples like the deque; otherwise it forms the images itself
     host_symmetries = not device_buffer or buffer.nsym == 1
@@ -317,13 +353,18 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         try:
             if selfplay_precision not in (None, "exact"):
                 model_candidate.set_eval_precision(selfplay_precision)
+            cap_kw = {} if playout_cap is None else {"playout_cap": playout_cap}
             examples, winners, drv = selfplay_games(sp_model, GameClass, n_local, n_simulations, cpuct, temp_fn,
                                                     dirichlet_alpha, dirichlet_epsilon, dirichlet_n_moves,
                                                     max_moves=max_moves, board_size=board_size,
-                                                    use_symmetries=host_symmetries)
+                                                    use_symmetries=host_symmetries, **cap_kw)
         finally:
             if selfplay_precision not in (None, "exact"):
                 model_candidate.set_eval_precision("exact")
+        pol_w = None
+        if playout_cap is not None:   # the examples' 4th field leaves them here: the rest of the loop sees 3-tuples
+            pol_w = np.array([e[3] for e in examples], dtype=np.float32)
+            examples = [e[:3] for e in examples]
         score_before = score_after = None
         if score_new_games:   # before the examples enter the buffer: the net has never trained on them
             score_before = _score_new_games(model_candidate, examples, score_max_examples)
@@ -331,7 +372,13 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                 print(_score_line("before training", score_before))
         if surprise_weight is not None and examples:
             kl = _score_surprise(model_candidate, examples)
-            buffer.add_positions(examples, surprise=kl, mix=surprise_weight)
+            if pol_w is None:
+                buffer.add_positions(examples, surprise=kl, mix=surprise_weight)
+            else:   # a fast position's policy target is not trusted: no surprise, the uniform share only
+                kl = kl[:, 0] * torch.from_numpy((pol_w > 0).astype(np.float32)).to(kl.device)
+                buffer.add_positions(examples, surprise=kl, mix=surprise_weight, policy_weight=pol_w)
+        elif pol_w is not None:
+            buffer.add_positions(examples, policy_weight=pol_w)
         elif device_buffer:
             buffer.add_positions(examples)
         else:
@@ -348,6 +395,11 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             for epoch in range(epochs_per_iter):
                 te = time.time()
                 for _ in range(n_batches):
+                    if playout_cap is not None:
+                        s, p, z, pw = (buffer.sample(batch_size, with_policy_weight=True) if surprise_weight is None
+                                       else buffer.sample_weighted(batch_size, with_policy_weight=True))
+                        loss_info = model_candidate.train_batch_device(s, p, z, epochs=1, policy_weight=pw)
+                        continue
                     s, p, z = (buffer.sample(batch_size) if surprise_weight is None
                                else buffer.sample_weighted(batch_size))
                     if device_buffer:   # the synchronous step: a skipped step is redone as on the host path
@@ -367,7 +419,10 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             history.append({"iteration": it, "new_games_before": score_before, "new_games_after": score_after,
                             "last_train_loss": loss_info, "ema_decay": ema_decay,
                             "surprise_weight": surprise_weight,
-                            "buffer_ess": None if surprise_weight is None else buffer.effective_sample_size()})
+                            "buffer_ess": None if surprise_weight is None else buffer.effective_sample_size(),
+                            "playout_cap": None if playout_cap is None else
+                            {"p_full": playout_cap[0], "fast_sims": playout_cap[1],
+                             "full_moves": drv.full_moves, "fast_moves": drv.fast_moves}})
 
         te = time.time()
         # with EMA on, the gated net is the average of the candidate's weights, not its last step
@@ -406,6 +461,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
         save_replay_buffer(buffer.to_host() if device_buffer else buffer, buffer_path)
         if surprise_weight is not None:
             np.save(weights_path, buffer.get_weights())
+        if playout_cap is not None:
+            np.save(pweights_path, buffer.get_policy_weights())
         if main:
             print(f"iteration {it} done in {(time.time() - t0) / 60:.2f} min; winners {winners}")
     if main:

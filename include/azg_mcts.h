@@ -59,6 +59,15 @@ int32_t azg_mcts_destroy(azg_mcts* h);
 int32_t azg_mcts_set_root(azg_mcts* h, int32_t g, const int8_t* board, int32_t player, int32_t last_r,
                           int32_t last_c, int32_t cap1, int32_t cap2, int32_t move_number);
 
+/* Per game slot: the simulation budget of its searches and whether their root may get
+ * Dirichlet noise (playout cap randomization: a cheap move is searched with few simulations
+ * and no noise).  Both take effect at the slot's next azg_mcts_set_root and hold until set
+ * again; azg_mcts_clear keeps them.  A negative value means the forest's own
+ * cfg.n_simulations / cfg.add_dirichlet_noise, which is also what a slot starts with: a
+ * forest that never calls this behaves as before.  The noise condition on the move number
+ * (apply_dirichlet_n_first_moves) applies as always. */
+int32_t azg_mcts_set_budget(azg_mcts* h, int32_t g, int32_t n_simulations, int32_t root_noise);
+
 /* Run every game with a search in progress until it needs an evaluation or its
  * move is done.  Writes the pending leaves of all games, in game order, as
  * float32 [n][3][size][size] (reference get_encoded_state) into `leaves`

@@ -181,6 +181,19 @@ int32_t azg_pv_train_backward(azg_pv* h, const float* x, const float* pis,
                               const float* zs, int32_t batch, float* losses,
                               void* stream);
 
+/* azg_pv_train_backward with per-example loss weights: wp (policy) and wv (value), device
+ * fp32 [batch], either may be NULL (= all ones).  The losses become
+ *   policy_loss = (1/batch) sum_b wp[b] KL_b,  value_loss = (1/batch) sum_b wv[b] (v_b - z_b)^2
+ * -- the divisor stays `batch`, not the sum of the weights -- and each board's gradient seeds
+ * are the unweighted ones times its weight.  Weights of 1.0 give azg_pv_train_backward's
+ * bits; with both pointers NULL exactly its kernels are launched.  A zero-weight board still
+ * passes through the forward and the batch statistics of every BN.  The values are not
+ * checked (they are on the device): callers pass finite weights >= 0.
+ * azg_pv_train_fp32_once applies to this call as to the plain one. */
+int32_t azg_pv_train_backward_weighted(azg_pv* h, const float* x, const float* pis,
+                                       const float* zs, const float* wp, const float* wv,
+                                       int32_t batch, float* losses, void* stream);
+
 /* clip_grad_norm_(max_norm) over the bound grads (call after any DP all-reduce
  * of the grad buffer), then one Adam step (torch semantics: L2-coupled weight
  * decay, bias correction for `step`, which is the post-increment step count).
@@ -221,6 +234,14 @@ int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, const float
                              int32_t cap_pos, int32_t head, int32_t count, int32_t nsym,
                              const int64_t* ids, int32_t batch,
                              float* x, float* pi_out, float* z_out, void* stream);
+
+/* One fp32 value per position of the same ring (vals [cap_pos], by slot: the policy loss
+ * weight), gathered for the same image ids: out[b] = vals[slot of image ids[b]], with
+ * azg_pv_replay_gather's id -> slot map, clamping and argument checks.  One launch,
+ * asynchronous on `stream`, no allocation. */
+int32_t azg_pv_replay_gather_weight(const float* vals, int32_t cap_pos, int32_t head,
+                                    int32_t count, int32_t nsym, const int64_t* ids,
+                                    int32_t batch, float* out, void* stream);
 
 /* Surprise-weighted sampling from the same ring (handle-free; three entry points beside
  * azg_pv_replay_gather, which they feed and do not change).  Every position carries a
