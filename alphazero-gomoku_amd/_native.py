@@ -92,6 +92,10 @@ _SIGS = {
     "azg_pv_train_backward_weighted": (ctypes.c_int32, [_P, _P, _P, _P, _P, _P, ctypes.c_int32, _P, _P]),
     "azg_pv_replay_gather_weight": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, _P, ctypes.c_int32, _P, _P]),
+    "azg_pv_replay_canon_keys": (ctypes.c_int32, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                  _P, _P, _P]),
+    "azg_pv_replay_average": (ctypes.c_int32, [_P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 PROF_CLASSES = ("conv3x3", "stem", "heads", "train_conv", "train_wgrad", "train_other", "tower", "tower16", "board",

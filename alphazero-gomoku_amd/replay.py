@@ -29,6 +29,15 @@ Also opt-in, and independent of the sampling weight: one POLICY LOSS WEIGHT per 
 (azg_pv_replay_gather_weight) for ``train_batch_device(policy_weight=...)`` -- playout cap
 randomization stores 0.0 for positions searched at the small budget.  It does not exist
 until the first call that passes weights; ``to_host`` and the pickle never carry it.
+
+Also opt-in: POSITION AVERAGING (``set_target_averaging(True)``).  The ring holds the same
+board many times -- the empty board once per game, openings that differ by a rotation or a
+flip, transpositions -- each copy with its own noisy search policy and its own +-1 outcome.
+With averaging on, ``refresh_averages`` (csrc/pv_replay_average.hip: a canonical 64-bit key per
+position, torch's stable sort, an exact board comparison and an fp64 mean per group) derives
+pi_avg / z_avg / pw_avg once per buffer change, and the unchanged gather reads those arrays in
+place of the raw ones: no launch is added per batch, and which positions are drawn is not
+touched.  The raw targets stay what ``to_host``, the pickle and the sidecars carry.
 """
 from __future__ import annotations
 
@@ -99,6 +108,11 @@ class DeviceReplayBuffer:
         self._prefix_ok = False    # False whenever the weights or the ring have moved since the last scan
         # policy loss weights: [cap_pos] float32 by slot, nothing until the first call that passes them
         self._pw = None
+        # position averaging: nothing of it exists until set_target_averaging(True)
+        self._avg_on = False
+        self._avg = None           # dict of device arrays (see _ensure_averages)
+        self._avg_ok = False       # False whenever the ring, the policy weights or the setting moved since the last refresh
+        self._avg_pw = False       # whether the last refresh wrote pw_avg
 
     def __len__(self) -> int:
         return self.count * self.nsym
@@ -190,6 +204,7 @@ class DeviceReplayBuffer:
             self._pw[tail:tail + first].fill_(1.0)
             self._pw[0:n - first].fill_(1.0)
         self._prefix_ok = False
+        self._avg_ok = False
         over = self.count + n - self.cap_pos
         if over > 0:
             self.head = (self.head + over) % self.cap_pos
@@ -255,6 +270,7 @@ class DeviceReplayBuffer:
         first = min(self.count, self.cap_pos - self.head)
         self._pw[self.head:self.head + first].copy_(stage[:first], non_blocking=True)
         self._pw[0:self.count - first].copy_(stage[first:], non_blocking=True)
+        self._avg_ok = False
 
     def get_policy_weights(self) -> np.ndarray:
         """The policy loss weights of the positions held, float32 [count] in ring order (all
@@ -269,10 +285,102 @@ class DeviceReplayBuffer:
         without a launch or an allocation of the ring's array, for a buffer without them)."""
         if self._pw is None:
             return torch.ones(batch_size, dtype=torch.float32, device=self.device)
+        vals = self._avg["pw_avg"] if self._avg_on else self._pw   # refreshed by the caller's _targets()
         w = torch.empty(batch_size, dtype=torch.float32, device=self.device)
-        check(self.lib.azg_pv_replay_gather_weight(ptr(self._pw), self.cap_pos, self.head, self.count, self.nsym,
+        check(self.lib.azg_pv_replay_gather_weight(ptr(vals), self.cap_pos, self.head, self.count, self.nsym,
                                                    ptr(d_ids), batch_size, ptr(w), st), self.lib)
         return w
+
+    # ------------------------------------------------------ position averaging
+    @property
+    def target_averaging(self) -> bool:
+        return self._avg_on
+
+    def set_target_averaging(self, on: bool) -> None:
+        """Train on the mean targets of positions with the same board (nsym = 8: up to a
+        rotation or a flip; nsym = 1: exact repeats).  Off, the default, samples the raw
+        targets bit for bit and makes no new call."""
+        on = bool(on)
+        if on != self._avg_on:
+            self._avg_on = on
+            self._avg_ok = False
+
+    def _ensure_averages(self) -> None:
+        if self._avg is None:
+            dev, c = self.device, self.cap_pos
+            self._avg = {"keys": torch.zeros(c, dtype=torch.int64, device=dev),       # by ring index
+                         "syms": torch.zeros(c, dtype=torch.int8, device=dev),        # by ring index
+                         "pi_avg": torch.zeros((c, _PIX), dtype=torch.float32, device=dev),   # by slot, like pis
+                         "z_avg": torch.zeros(c, dtype=torch.float32, device=dev),    # by slot
+                         "pw_avg": None,                                              # by slot, with _pw
+                         "group_first": torch.zeros(c, dtype=torch.int32, device=dev),   # by ring index
+                         "group_size": torch.zeros(c, dtype=torch.int32, device=dev)}    # by ring index
+
+    def refresh_averages(self) -> None:
+        """Recompute the averaged targets if the ring, the policy weights or the setting
+        changed since they were last computed (sample and sample_weighted call this).  Two
+        kernels around torch's stable sort; no host sync."""
+        if not self._avg_on or self._avg_ok or self.count < 1:
+            return
+        self._ensure_averages()
+        a = self._avg
+        if self._pw is not None and a["pw_avg"] is None:
+            a["pw_avg"] = torch.ones(self.cap_pos, dtype=torch.float32, device=self.device)
+        n = self.count
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            check(self.lib.azg_pv_replay_canon_keys(ptr(self.stones), self.cap_pos, self.head, n, self.nsym,
+                                                    ptr(a["keys"]), ptr(a["syms"]), st), self.lib)
+            keys_sorted, perm = torch.sort(a["keys"][:n], stable=True)   # equal keys adjacent, in ring order
+            check(self.lib.azg_pv_replay_average(
+                ptr(self.stones), ptr(self.pis), ptr(self.zs), ptr(self._pw), self.cap_pos, self.head, n,
+                ptr(keys_sorted), ptr(perm), ptr(a["syms"]), ptr(a["pi_avg"]), ptr(a["z_avg"]),
+                ptr(a["pw_avg"]) if self._pw is not None else None, ptr(a["group_first"]), ptr(a["group_size"]), st),
+                self.lib)
+            # the caching allocator hands keys_sorted / perm back only to work queued later on
+            # this stream, so they may go out of scope here
+        self._avg_pw = self._pw is not None
+        self._avg_ok = True
+
+    def _targets(self):
+        """(pis, zs) the gather reads: the averaged arrays, refreshed if stale, while
+        averaging is on."""
+        if not self._avg_on:
+            return self.pis, self.zs
+        self.refresh_averages()
+        return self._avg["pi_avg"], self._avg["z_avg"]
+
+    def duplicate_stats(self) -> dict:
+        """{"positions", "groups", "largest"}: positions held, groups of equal boards among
+        them, and the largest group's size (needs averaging on).  Synchronises: for logging."""
+        sizes = self.get_group_sizes()
+        firsts = self._ring_order_int("group_first")
+        groups = int((firsts == np.arange(len(firsts))).sum())
+        return {"positions": int(self.count), "groups": groups, "largest": int(sizes.max()) if len(sizes) else 0}
+
+    def _ring_order_int(self, name: str) -> np.ndarray:
+        if not self._avg_on:
+            raise RuntimeError("position averaging is off: call set_target_averaging(True) first")
+        if self.count < 1:
+            return np.zeros(0, dtype=np.int32)
+        self.refresh_averages()
+        return self._avg[name][:self.count].cpu().numpy()
+
+    def get_group_sizes(self) -> np.ndarray:
+        """int32 [count] in ring order: the size of each position's group.  Synchronises."""
+        return self._ring_order_int("group_size")
+
+    def get_averaged_targets(self) -> dict:
+        """Host arrays in ring order: "pi" [count,225], "z" [count], "policy_weight" [count]
+        (None for a buffer without policy weights), "group_first", "group_size", "keys"
+        (uint64), "syms".  Synchronises: for tests and inspection."""
+        first = self._ring_order_int("group_first")
+        a, n = self._avg, self.count
+        order = (self.head + torch.arange(n, device=self.device)) % self.cap_pos
+        return {"pi": a["pi_avg"][order].cpu().numpy(), "z": a["z_avg"][order].cpu().numpy(),
+                "policy_weight": a["pw_avg"][order].cpu().numpy() if self._avg_pw else None,
+                "group_first": first, "group_size": a["group_size"][:n].cpu().numpy(),
+                "keys": a["keys"][:n].cpu().numpy().view(np.uint64), "syms": a["syms"][:n].cpu().numpy()}
 
     # --------------------------------------------------------------- sampling
     def draw_ids(self, batch_size: int) -> list:
@@ -295,7 +403,8 @@ class DeviceReplayBuffer:
             s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
             p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
             z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
-            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(self.pis), ptr(self.zs), self.cap_pos,
+            pis, zs = self._targets()
+            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(pis), ptr(zs), self.cap_pos,
                                                 self.head, self.count, self.nsym, ptr(d_ids), batch_size,
                                                 ptr(s), ptr(p), ptr(z),
                                                 torch.cuda.current_stream(dev).cuda_stream), self.lib)
@@ -340,7 +449,8 @@ class DeviceReplayBuffer:
             s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
             p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
             z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
-            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(self.pis), ptr(self.zs), self.cap_pos,
+            pis, zs = self._targets()
+            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(pis), ptr(zs), self.cap_pos,
                                                 self.head, self.count, self.nsym, ptr(d_ids), batch_size,
                                                 ptr(s), ptr(p), ptr(z), st), self.lib)
             if with_policy_weight:

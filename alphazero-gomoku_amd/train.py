@@ -209,7 +209,7 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     score_max_examples: int = 4096, history: Optional[list] = None,
                     ema_decay: Optional[float] = None, surprise_weight: Optional[float] = None,
                     playout_cap_prob: Optional[float] = None, playout_cap_fast_sims: Optional[int] = None,
-                    **reference_worker_kwargs):
+                    average_duplicates: bool = False, **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -277,7 +277,20 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     surprise_weight also on, the surprise of fast positions is set to 0 before they enter
     the buffer -- their policy target is not trusted, so they get the uniform share only.
     score_new_games is unchanged: its policy metrics then include the fast positions.
-    None, the default, makes none of these calls."""
+    None, the default, makes none of these calls.
+
+    average_duplicates (needs device_buffer=True): position averaging.  Positions in the
+    buffer with the same board -- up to a rotation or a flip -- train on the mean of their
+    policy targets (weighted by their policy loss weights, so fast playout-cap searches never
+    enter it) and the mean of their outcomes (DeviceReplayBuffer.set_target_averaging); the
+    means are recomputed on the device once per buffer change, not per batch.  Which positions
+    are drawn is unchanged, so it combines freely with surprise_weight and playout_cap_*.  The
+    buffer pickle and the sidecars keep the raw targets.  history entries carry
+    "buffer_groups": {"positions", "groups", "largest"} of the buffer the iteration trained
+    on, None when off.  No effect on playing strength has been measured.  False, the default,
+    makes none of these calls."""
+    if average_duplicates and not device_buffer:
+        raise ValueError("average_duplicates needs device_buffer=True (the host ReplayBuffer does not merge positions)")
     if (playout_cap_prob is None) != (playout_cap_fast_sims is None):
         raise ValueError("playout_cap_prob and playout_cap_fast_sims must be given together")
     playout_cap = None
@@ -325,6 +338,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     if device_buffer:
         from replay import new_device_buffer
         buffer = new_device_buffer(load_replay_buffer(buffer_path, capacity=buffer_size), buffer_size, device)
+        if average_duplicates:
+            buffer.set_target_averaging(True)
     else:
         buffer = load_replay_buffer(buffer_path, capacity=buffer_size) or ReplayBuffer(capacity=buffer_size)
     weights_path = os.path.join(model_dir, f"replay_weights_latest{suffix}.npy")
@@ -422,7 +437,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                             "buffer_ess": None if surprise_weight is None else buffer.effective_sample_size(),
                             "playout_cap": None if playout_cap is None else
                             {"p_full": playout_cap[0], "fast_sims": playout_cap[1],
-                             "full_moves": drv.full_moves, "fast_moves": drv.fast_moves}})
+                             "full_moves": drv.full_moves, "fast_moves": drv.fast_moves},
+                            "buffer_groups": buffer.duplicate_stats() if average_duplicates else None})
 
         te = time.time()
         # with EMA on, the gated net is the average of the candidate's weights, not its last step

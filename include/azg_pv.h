@@ -290,6 +290,53 @@ int32_t azg_pv_replay_prefix(const uint32_t* weights, int32_t cap_pos, int32_t h
 int32_t azg_pv_replay_draw(const uint64_t* prefix, int32_t count, int32_t nsym, const uint64_t* rnd,
                            int32_t batch, int64_t* ids, void* stream);
 
+/* Position averaging in the same ring (handle-free; two entry points beside
+ * azg_pv_replay_gather, which reads their outputs through the pis / zs / vals pointers it
+ * always took and is not changed).  Positions with the same board -- with nsym = 8: up to a
+ * rotation or a flip -- get the mean of their targets.  Ring index i is slot
+ * (head + i) % cap_pos.  Everything is an integer or an fp64 sum in ring order rounded once,
+ * so a host restatement gives the same bits; no atomics.
+ *
+ * azg_pv_replay_canon_keys: keys_out[i] (64 bits in an int64) and syms_out[i] (int8) for ring
+ * index i < count.  splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) *
+ * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31 (mod 2^64).
+ * Z(j, v) = splitmix64(2 j + v - 1) for square j and stone v in {1, 2}.  Image s of a position
+ * is img_s[j] = stones[src(j, s)], src being azg_pv_replay_gather's map (image square j of
+ * symmetry s reads board square src), and h_s = the XOR of Z(j, img_s[j]) over its non-empty
+ * squares (0 for the empty board).  nsym = 8: key = min_s h_s compared as unsigned, sym = the
+ * smallest s attaining it -- all 8 images of a board get one key, and img_sym is the same
+ * CANONICAL BOARD for all of them.  nsym = 1: key = h_0, sym = 0 (exact repeats only).
+ * Checked before any device call: null stones, keys_out or syms_out, nsym not 1 or 8,
+ * cap_pos < 1, count outside [1, cap_pos], head outside [0, cap_pos).  One launch.
+ *
+ * azg_pv_replay_average: keys_sorted [count] are the keys in ascending order of a STABLE sort
+ * and perm [count] (int64) the ring index at each sorted place (equal keys adjacent, in ring
+ * order); syms [count] is indexed by ring index.  Place k starts a group when k == 0, its key
+ * differs from place k - 1's, or its canonical board stones[src(j, sym)] differs from place
+ * k - 1's in any square: unequal boards never merge, a key collision can only split a group.
+ * For a group with members m = 1..n in ring order, c_m = member m's sym, in fp64 in member
+ * order:  W = sum pw_m,  A[j] = sum pw_m * pis_m[src(j, c_m)]  for canonical square j,
+ * Zs = sum zs_m.  pw (by slot) and pw_avg are both NULL (every pw_m = 1.0, nothing written)
+ * or both set.  Written for every member -- pi_avg [cap_pos][225], z_avg and pw_avg
+ * [cap_pos] by SLOT, as the gather reads them; group_first and group_size [count] int32 by
+ * ring index:
+ *   pi_avg_m[src(j, c_m)] = (float)(A[j] / W) if W > 0, else pis_m[src(j, c_m)]
+ *   z_avg_m = (float)(Zs / n)     pw_avg_m = (float)(W / n)
+ *   group_first = the ring index of the group's oldest member     group_size = n
+ * A group of one comes out bit-identical to its raw targets.  A perm entry outside
+ * [0, count) is clamped into it.  Checked before any device call: null stones, pis, zs,
+ * keys_sorted, perm, syms, pi_avg, z_avg, group_first or group_size, exactly one of pw /
+ * pw_avg null, cap_pos < 1, count outside [1, cap_pos], head outside [0, cap_pos).  Two
+ * launches: the group starts (one wavefront per place), then one workgroup per group, which
+ * walks its members 256 at a time -- a group may be the whole ring.
+ * Both are asynchronous on `stream` and allocate nothing. */
+int32_t azg_pv_replay_canon_keys(const int8_t* stones, int32_t cap_pos, int32_t head, int32_t count,
+                                 int32_t nsym, int64_t* keys_out, int8_t* syms_out, void* stream);
+int32_t azg_pv_replay_average(const int8_t* stones, const float* pis, const float* zs, const float* pw,
+                              int32_t cap_pos, int32_t head, int32_t count, const int64_t* keys_sorted,
+                              const int64_t* perm, const int8_t* syms, float* pi_avg, float* z_avg,
+                              float* pw_avg, int32_t* group_first, int32_t* group_size, void* stream);
+
 /* Score eval-forward outputs against targets without a train step (handle-free): the two
  * loss terms of the reference's train_batch -- KLDivLoss(batchmean) on log_softmax(logits)
  * and MSELoss on the value, network.py:162-163,216-219 -- per board and summed, plus policy
