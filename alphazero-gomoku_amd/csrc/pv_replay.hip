@@ -5,8 +5,9 @@
 //   planes  <- Gomoku.get_encoded_state (games/gomoku.py:130-150)
 //   image s <- MCTS.symmetries (mcts/new_mcts_alpha.py:42-56): np.rot90 by k = s / 2
 //              (counter-clockwise), then a column flip when s is odd.
-// Every output value is a copy or a 0/1 constant: the result equals numpy's bit for bit.
-#include "pv_internal.h"
+// Every output value is a copy or a 0/1 constant: the result equals numpy's bit for bit.  The ring's
+// slot map, sym_src_sq and the entry points' argument checks are pv_replay.h's.
+#include "pv_replay.h"
 
 namespace azg {
 
@@ -18,16 +19,15 @@ __global__ __launch_bounds__(256) void replay_gather_kernel(
     float* __restrict__ pi_out, float* __restrict__ z_out)
 {
     const int b = blockIdx.x;
-    // an id outside [0, count * nsym) is clamped: it never reads outside the ring
+    // an id outside [0, count * nsym) is clamped: it never reads outside the ring (as in the kernel below)
     const int64_t last = (int64_t)count * nsym - 1;
     int64_t id = ids[b];
     id = id < 0 ? 0 : (id > last ? last : id);
     const int s = (int)(id % nsym);
-    const int pos = (int)(((int64_t)head + id / nsym) % cap_pos);
+    const int pos = ring_slot(head, id / nsym, cap_pos);
     const int j = threadIdx.x;
     if (j < PIX) {
-        const int y = j / BOARD, xx = j - y * BOARD;
-        const int src = sym_src(y, xx, s);   // pv_common.h
+        const int src = sym_src_sq(j, s);
         const int8_t v = stones[(size_t)pos * PIX + src];
         float* xo = x + (size_t)b * 3 * PIX;
         xo[j] = v == 1 ? 1.f : 0.f;
@@ -49,8 +49,7 @@ __global__ __launch_bounds__(256) void replay_gather_weight_kernel(
     const int64_t last = (int64_t)count * nsym - 1;
     int64_t id = ids[b];
     id = id < 0 ? 0 : (id > last ? last : id);
-    const int pos = (int)(((int64_t)head + id / nsym) % cap_pos);
-    out[b] = vals[pos];
+    out[b] = vals[ring_slot(head, id / nsym, cap_pos)];
 }
 
 }  // namespace azg
@@ -60,17 +59,13 @@ extern "C" int32_t azg_pv_replay_gather(const int8_t* stones, const float* pis, 
                                         float* x, float* pi_out, float* z_out, void* stream)
 {
     using namespace azg;
-    if (!stones || !pis || !zs || !ids || !x || !pi_out || !z_out)
-        return set_error("azg_pv_replay_gather: null argument", hipSuccess);
-    if (nsym != 1 && nsym != 8) return set_error("azg_pv_replay_gather: nsym must be 1 or 8", hipSuccess);
-    if (batch < 1) return set_error("azg_pv_replay_gather: batch must be >= 1", hipSuccess);
-    if (cap_pos < 1) return set_error("azg_pv_replay_gather: cap_pos must be >= 1", hipSuccess);
-    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_gather: count outside [1, cap_pos]", hipSuccess);
-    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_gather: head outside [0, cap_pos)", hipSuccess);
+    if (AZG_NULL_ARG(stones) || AZG_NULL_ARG(pis) || AZG_NULL_ARG(zs) || AZG_NULL_ARG(ids) || AZG_NULL_ARG(x) ||
+        AZG_NULL_ARG(pi_out) || AZG_NULL_ARG(z_out))
+        return 1;
+    if (bad_nsym(__func__, nsym) || bad_batch(__func__, batch) || bad_ring(__func__, cap_pos, head, count)) return 1;
     hipLaunchKernelGGL(replay_gather_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, stones, pis, zs,
                        cap_pos, head, count, nsym, ids, x, pi_out, z_out);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_gather: launch", e);
-    return 0;
+    return launched(__func__, "launch");
 }
 
 extern "C" int32_t azg_pv_replay_gather_weight(const float* vals, int32_t cap_pos, int32_t head, int32_t count,
@@ -78,14 +73,9 @@ extern "C" int32_t azg_pv_replay_gather_weight(const float* vals, int32_t cap_po
                                                void* stream)
 {
     using namespace azg;
-    if (!vals || !ids || !out) return set_error("azg_pv_replay_gather_weight: null argument", hipSuccess);
-    if (nsym != 1 && nsym != 8) return set_error("azg_pv_replay_gather_weight: nsym must be 1 or 8", hipSuccess);
-    if (batch < 1) return set_error("azg_pv_replay_gather_weight: batch must be >= 1", hipSuccess);
-    if (cap_pos < 1) return set_error("azg_pv_replay_gather_weight: cap_pos must be >= 1", hipSuccess);
-    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_gather_weight: count outside [1, cap_pos]", hipSuccess);
-    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_gather_weight: head outside [0, cap_pos)", hipSuccess);
+    if (AZG_NULL_ARG(vals) || AZG_NULL_ARG(ids) || AZG_NULL_ARG(out)) return 1;
+    if (bad_nsym(__func__, nsym) || bad_batch(__func__, batch) || bad_ring(__func__, cap_pos, head, count)) return 1;
     hipLaunchKernelGGL(replay_gather_weight_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, vals, cap_pos, head, count, nsym, ids, batch, out);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_gather_weight: launch", e);
-    return 0;
+    return launched(__func__, "launch");
 }

@@ -1,6 +1,6 @@
 // Position averaging in the replay ring (include/azg_pv.h azg_pv_replay_canon_keys,
-// azg_pv_replay_average), beside the gather of pv_replay.hip, which is unchanged: it reads the
-// arrays written here through the pointers it always took.
+// azg_pv_replay_average), beside the gather of pv_replay.hip, which reads the arrays written
+// here through the pointers it always took; ring_slot and the argument checks are pv_replay.h's.
 //   canon_keys  one 64-bit key per position, equal for all 8 dihedral images of a board
 //               (the minimum of the images' Zobrist-style hashes), and the image that attains it;
 //   average     positions whose canonical boards are equal (adjacent after the caller's stable
@@ -9,7 +9,7 @@
 //               orientation.
 // Keys are integers; the means are fp64 sums in ring order rounded once: a host restatement
 // (tests/replay_average_reference.py) reproduces every bit.  No atomics anywhere.
-#include "pv_internal.h"
+#include "pv_replay.h"
 
 namespace azg {
 
@@ -32,12 +32,6 @@ __device__ __forceinline__ uint64_t wave_xor(uint64_t v)
     return v;
 }
 
-__device__ __forceinline__ int sym_src_sq(int j, int s)
-{
-    const int y = j / BOARD;
-    return sym_src(y, j - y * BOARD, s);   // pv_common.h
-}
-
 // ------------------------------------------------------------------------------- keys
 constexpr int KEY_WAVES = 4;   // 256 threads: 225 squares, the last wave only partly used
 
@@ -57,7 +51,7 @@ __global__ __launch_bounds__(256) void replay_canon_keys_kernel(const int8_t* __
 #pragma unroll
     for (int s = 0; s < 8; ++s) src[s] = j < PIX ? sym_src_sq(j, s) : 0;
     for (int i = blockIdx.x; i < count; i += gridDim.x) {
-        const int slot = (int)(((int64_t)head + i) % cap_pos);
+        const int slot = ring_slot(head, i, cap_pos);
         if (j < PIX) board[j] = stones[(size_t)slot * PIX + j];
         __syncthreads();
 #pragma unroll
@@ -118,8 +112,8 @@ __global__ __launch_bounds__(256) void replay_group_flags_kernel(const int8_t* _
     bool start = k == 0 || keys_sorted[k] != keys_sorted[k - 1];
     if (!start) {
         const int q = ring_index(perm, k - 1, count);
-        const int8_t* a = stones + (size_t)(((int64_t)head + r) % cap_pos) * PIX;
-        const int8_t* b = stones + (size_t)(((int64_t)head + q) % cap_pos) * PIX;
+        const int8_t* a = stones + (size_t)ring_slot(head, r, cap_pos) * PIX;
+        const int8_t* b = stones + (size_t)ring_slot(head, q, cap_pos) * PIX;
         const int ca = syms[r] & 7, cb = syms[q] & 7;
         bool differ = false;
         for (int j = lane; j < PIX; j += 64) differ |= a[sym_src_sq(j, ca)] != b[sym_src_sq(j, cb)];
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(256) void replay_average_kernel(
         float my_w = 0.f, my_z = 0.f;
         if (lane < len) {
             const int r = ring_index(perm, k + base + lane, count);
-            my_slot = (int)(((int64_t)head + r) % cap_pos);
+            my_slot = ring_slot(head, r, cap_pos);
             my_sym = syms[r] & 7;
             my_w = pw ? pw[my_slot] : 1.f;
             my_z = zs[my_slot];
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(256) void replay_average_kernel(
         int my_slot = 0, my_sym = 0;
         if (lane < len) {
             const int r = ring_index(perm, k + base + lane, count);
-            my_slot = (int)(((int64_t)head + r) % cap_pos);
+            my_slot = ring_slot(head, r, cap_pos);
             my_sym = syms[r] & 7;
             if (wave == 0) {
                 z_avg[my_slot] = zf;
@@ -257,18 +251,12 @@ extern "C" int32_t azg_pv_replay_canon_keys(const int8_t* stones, int32_t cap_po
                                             int32_t nsym, int64_t* keys_out, int8_t* syms_out, void* stream)
 {
     using namespace azg;
-    if (!stones) return set_error("azg_pv_replay_canon_keys: stones is null", hipSuccess);
-    if (!keys_out) return set_error("azg_pv_replay_canon_keys: keys_out is null", hipSuccess);
-    if (!syms_out) return set_error("azg_pv_replay_canon_keys: syms_out is null", hipSuccess);
-    if (nsym != 1 && nsym != 8) return set_error("azg_pv_replay_canon_keys: nsym must be 1 or 8", hipSuccess);
-    if (cap_pos < 1) return set_error("azg_pv_replay_canon_keys: cap_pos must be >= 1", hipSuccess);
-    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_canon_keys: count outside [1, cap_pos]", hipSuccess);
-    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_canon_keys: head outside [0, cap_pos)", hipSuccess);
+    if (AZG_NULL_ARG(stones) || AZG_NULL_ARG(keys_out) || AZG_NULL_ARG(syms_out)) return 1;
+    if (bad_nsym(__func__, nsym) || bad_ring(__func__, cap_pos, head, count)) return 1;
     const int grid = count < 4096 ? count : 4096;
     hipLaunchKernelGGL(replay_canon_keys_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, stones,
                        cap_pos, head, count, nsym, keys_out, syms_out);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_canon_keys: launch", e);
-    return 0;
+    return launched(__func__, "launch");
 }
 
 extern "C" int32_t azg_pv_replay_average(const int8_t* stones, const float* pis, const float* zs, const float* pw,
@@ -277,27 +265,17 @@ extern "C" int32_t azg_pv_replay_average(const int8_t* stones, const float* pis,
                                          float* pw_avg, int32_t* group_first, int32_t* group_size, void* stream)
 {
     using namespace azg;
-    if (!stones) return set_error("azg_pv_replay_average: stones is null", hipSuccess);
-    if (!pis) return set_error("azg_pv_replay_average: pis is null", hipSuccess);
-    if (!zs) return set_error("azg_pv_replay_average: zs is null", hipSuccess);
-    if (!keys_sorted) return set_error("azg_pv_replay_average: keys_sorted is null", hipSuccess);
-    if (!perm) return set_error("azg_pv_replay_average: perm is null", hipSuccess);
-    if (!syms) return set_error("azg_pv_replay_average: syms is null", hipSuccess);
-    if (!pi_avg) return set_error("azg_pv_replay_average: pi_avg is null", hipSuccess);
-    if (!z_avg) return set_error("azg_pv_replay_average: z_avg is null", hipSuccess);
-    if (!group_first) return set_error("azg_pv_replay_average: group_first is null", hipSuccess);
-    if (!group_size) return set_error("azg_pv_replay_average: group_size is null", hipSuccess);
-    if ((pw == nullptr) != (pw_avg == nullptr))
-        return set_error("azg_pv_replay_average: pw and pw_avg must both be null or both be set", hipSuccess);
-    if (cap_pos < 1) return set_error("azg_pv_replay_average: cap_pos must be >= 1", hipSuccess);
-    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_average: count outside [1, cap_pos]", hipSuccess);
-    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_average: head outside [0, cap_pos)", hipSuccess);
+    if (AZG_NULL_ARG(stones) || AZG_NULL_ARG(pis) || AZG_NULL_ARG(zs) || AZG_NULL_ARG(keys_sorted) ||
+        AZG_NULL_ARG(perm) || AZG_NULL_ARG(syms) || AZG_NULL_ARG(pi_avg) || AZG_NULL_ARG(z_avg) ||
+        AZG_NULL_ARG(group_first) || AZG_NULL_ARG(group_size))
+        return 1;
+    if (!pw != !pw_avg) return refused(__func__, "pw and pw_avg must both be null or both be set");
+    if (bad_ring(__func__, cap_pos, head, count)) return 1;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(replay_group_flags_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, st, stones, cap_pos,
                        head, count, keys_sorted, perm, syms, group_first);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_average: flags launch", e);
+    if (launched(__func__, "flags launch")) return 1;
     hipLaunchKernelGGL(replay_average_kernel, dim3((unsigned)count), dim3(256), 0, st, pis, zs, pw, cap_pos, head,
                        count, perm, syms, pi_avg, z_avg, pw_avg, group_first, group_size);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_average: average launch", e);
-    return 0;
+    return launched(__func__, "average launch");
 }

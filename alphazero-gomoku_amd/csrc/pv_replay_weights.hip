@@ -1,12 +1,12 @@
 // Surprise-weighted sampling from the replay ring (include/azg_pv.h azg_pv_replay_surprise_weights,
-// azg_pv_replay_prefix, azg_pv_replay_draw), beside the gather of pv_replay.hip, which is unchanged.
+// azg_pv_replay_prefix, azg_pv_replay_draw), beside the gather of pv_replay.hip, on pv_replay.h's ring.
 // A position's weight is an integer number of quanta (one unit of weight = 2^16 quanta), so
 //   prefix  the running sums in ring order are exact in any summation order, and
 //   draw    the chosen position is an integer function of the random words:
 //           t = floor(r * total / 2^64), j = the first position whose running sum exceeds t
 // -- a host restatement in integers reproduces every id.  Only surprise_weights computes in
 // floating point (fp64, operation order fixed by its contract).
-#include "pv_internal.h"
+#include "pv_replay.h"
 
 namespace azg {
 
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void replay_surprise_weights_kernel(const floa
         const double w = S > 0.0 ? (1.0 - mix) + mix * (double)n_sum * s / S : 1.0;
         const double q = w * kQuantaPerUnit;
         const uint32_t out = q >= kQuantaMax ? 2147483647u : (q <= 0.0 ? 0u : (uint32_t)llrint(q));
-        weights[(int)(((int64_t)at + k) % cap_pos)] = out;
+        weights[ring_slot(at, k, cap_pos)] = out;
     }
 }
 
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void replay_prefix_tiles_kernel(const
 #pragma unroll
     for (int t = 0; t < SCAN_ITEMS; ++t) {
         const int64_t j = base + t;
-        v[t] = j < count ? (uint64_t)weights[(int)(((int64_t)head + j) % cap_pos)] : 0;
+        v[t] = j < count ? (uint64_t)weights[ring_slot(head, j, cap_pos)] : 0;
         mine += v[t];
         v[t] = mine;   // inclusive within the thread's chunk
     }
@@ -182,40 +182,32 @@ extern "C" int32_t azg_pv_replay_surprise_weights(const float* surprise, int32_t
                                                   void* stream)
 {
     using namespace azg;
-    if (!surprise) return set_error("azg_pv_replay_surprise_weights: surprise is null", hipSuccess);
-    if (!weights) return set_error("azg_pv_replay_surprise_weights: weights is null", hipSuccess);
-    if (!(mix >= 0.0 && mix <= 1.0)) return set_error("azg_pv_replay_surprise_weights: mix outside [0, 1]", hipSuccess);
-    if (stride < 1) return set_error("azg_pv_replay_surprise_weights: stride must be >= 1", hipSuccess);
-    if (cap_pos < 1) return set_error("azg_pv_replay_surprise_weights: cap_pos must be >= 1", hipSuccess);
-    if (n < 1 || n > cap_pos) return set_error("azg_pv_replay_surprise_weights: n outside [1, cap_pos]", hipSuccess);
-    if (n_sum < n) return set_error("azg_pv_replay_surprise_weights: n_sum must be >= n", hipSuccess);
-    if (at < 0 || at >= cap_pos) return set_error("azg_pv_replay_surprise_weights: at outside [0, cap_pos)", hipSuccess);
+    if (AZG_NULL_ARG(surprise) || AZG_NULL_ARG(weights)) return 1;
+    if (!(mix >= 0.0 && mix <= 1.0)) return refused(__func__, "mix outside [0, 1]");
+    if (stride < 1) return refused(__func__, "stride must be >= 1");
+    if (bad_ring(__func__, cap_pos, at, n, "at", "n")) return 1;
+    if (n_sum < n) return refused(__func__, "n_sum must be >= n");
     hipLaunchKernelGGL(replay_surprise_weights_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, surprise, stride, n,
                        n_sum, mix, weights, cap_pos, at);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_surprise_weights: launch", e);
-    return 0;
+    return launched(__func__, "launch");
 }
 
 extern "C" int32_t azg_pv_replay_prefix(const uint32_t* weights, int32_t cap_pos, int32_t head, int32_t count,
                                         uint64_t* prefix, void* stream)
 {
     using namespace azg;
-    if (!weights) return set_error("azg_pv_replay_prefix: weights is null", hipSuccess);
-    if (!prefix) return set_error("azg_pv_replay_prefix: prefix is null", hipSuccess);
-    if (cap_pos < 1) return set_error("azg_pv_replay_prefix: cap_pos must be >= 1", hipSuccess);
-    if (count < 1 || count > cap_pos) return set_error("azg_pv_replay_prefix: count outside [1, cap_pos]", hipSuccess);
-    if (head < 0 || head >= cap_pos) return set_error("azg_pv_replay_prefix: head outside [0, cap_pos)", hipSuccess);
+    if (AZG_NULL_ARG(weights) || AZG_NULL_ARG(prefix) || bad_ring(__func__, cap_pos, head, count)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int ntiles = (int)(((int64_t)count + SCAN_TILE - 1) / SCAN_TILE);
     hipLaunchKernelGGL(replay_prefix_tiles_kernel, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, st, weights, cap_pos,
                        head, count, prefix);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_prefix: tiles launch", e);
+    if (launched(__func__, "tiles launch")) return 1;
     if (ntiles > 1) {
         hipLaunchKernelGGL(replay_prefix_totals_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, prefix, count, ntiles);
-        if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_prefix: totals launch", e);
+        if (launched(__func__, "totals launch")) return 1;
         hipLaunchKernelGGL(replay_prefix_offsets_kernel, dim3((unsigned)(ntiles - 1)), dim3(SCAN_THREADS), 0, st,
                            prefix, count);
-        if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_prefix: offsets launch", e);
+        if (launched(__func__, "offsets launch")) return 1;
     }
     return 0;
 }
@@ -224,14 +216,10 @@ extern "C" int32_t azg_pv_replay_draw(const uint64_t* prefix, int32_t count, int
                                       int32_t batch, int64_t* ids, void* stream)
 {
     using namespace azg;
-    if (!prefix) return set_error("azg_pv_replay_draw: prefix is null", hipSuccess);
-    if (!rnd) return set_error("azg_pv_replay_draw: rnd is null", hipSuccess);
-    if (!ids) return set_error("azg_pv_replay_draw: ids is null", hipSuccess);
-    if (count < 1) return set_error("azg_pv_replay_draw: count must be >= 1", hipSuccess);
-    if (nsym != 1 && nsym != 8) return set_error("azg_pv_replay_draw: nsym must be 1 or 8", hipSuccess);
-    if (batch < 1) return set_error("azg_pv_replay_draw: batch must be >= 1", hipSuccess);
+    if (AZG_NULL_ARG(prefix) || AZG_NULL_ARG(rnd) || AZG_NULL_ARG(ids)) return 1;
+    if (count < 1) return refused(__func__, "count must be >= 1");   // no cap_pos here: prefix is in ring order
+    if (bad_nsym(__func__, nsym) || bad_batch(__func__, batch)) return 1;
     hipLaunchKernelGGL(replay_draw_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        prefix, count, nsym, rnd, batch, ids);
-    if (hipError_t e = hipGetLastError()) return set_error("azg_pv_replay_draw: launch", e);
-    return 0;
+    return launched(__func__, "launch");
 }

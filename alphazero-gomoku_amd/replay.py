@@ -14,7 +14,8 @@ mcts/new_mcts_alpha.py) on the fly.
 Image numbering makes the two buffers interchangeable: image i of this buffer is
 element i of the host deque (position i // 8 in ring order, symmetry i % 8), and
 random.sample picks by index from (len, k) alone, so under the same random.seed
-``sample`` returns the host buffer's batch bit for bit.
+``sample`` returns the host buffer's batch bit for bit.  Every per-slot array is written
+through ``ring_spans`` (a write splits where the ring wraps) and read in ``_order()``.
 
 Opt-in, the ring also carries one WEIGHT per position (``add_positions(...,
 surprise=...)``, ``set_weights``) and ``sample_weighted`` draws positions in proportion to
@@ -71,6 +72,19 @@ def _images(S: np.ndarray, P: np.ndarray):
     return out
 
 
+def ring_spans(at: int, n: int, cap: int):
+    """A write of n <= cap items from slot ``at`` splits where it wraps: [(lo, hi, dst)], items [lo, hi) to slots dst..."""
+    first = min(n, cap - at)
+    return [(lo, hi, dst) for lo, hi, dst in ((0, first, at), (first, n, 0)) if hi > lo]
+
+
+def _pinned(values: np.ndarray, dtype) -> torch.Tensor:
+    """A pinned host copy; torch's host allocator keeps it alive until the copies queued from it have run."""
+    stage = torch.empty(values.shape, dtype=dtype, pin_memory=True)
+    stage.numpy()[...] = values
+    return stage
+
+
 def _stack(examples):
     S = np.stack([np.asarray(e[0]) for e in examples]).astype(np.float32, copy=False)
     P = np.stack([np.asarray(e[1]) for e in examples]).astype(np.float32, copy=False)
@@ -116,6 +130,29 @@ class DeviceReplayBuffer:
 
     def __len__(self) -> int:
         return self.count * self.nsym
+
+    def _ring(self):   # the (cap_pos, head, count) run of the native calls
+        return self.cap_pos, self.head, self.count
+
+    def _order(self) -> torch.Tensor:   # the slots in ring order (oldest first), a device index tensor [count]
+        return (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
+
+    def _write(self, dst, src, at: int) -> None:   # pinned host rows src into the per-slot array dst, from slot at on
+        for lo, hi, d in ring_spans(at, len(src), self.cap_pos):
+            dst[d:d + hi - lo].copy_(src[lo:hi], non_blocking=True)
+
+    def _fill(self, dst, at: int, n: int, value) -> None:   # value into n slots of the per-slot array dst, from slot at on
+        for lo, hi, d in ring_spans(at, n, self.cap_pos):
+            dst[d:d + hi - lo].fill_(value)
+
+    def _ring_moved(self) -> None:   # positions came or went: the prefix sums and the averages are stale
+        self._prefix_ok = self._avg_ok = False
+
+    def _weights_moved(self) -> None:   # the sampling weights changed: the prefix sums
+        self._prefix_ok = False
+
+    def _averaging_inputs_moved(self) -> None:   # the policy weights or the setting changed: the averages
+        self._avg_ok = False
 
     # ---------------------------------------------------------------- writing
     def add_positions(self, examples, surprise=None, mix: float = 0.5, policy_weight=None) -> None:
@@ -167,23 +204,16 @@ class DeviceReplayBuffer:
             if policy_weight is not None:
                 policy_weight = policy_weight[-self.cap_pos:]
         n = len(stones)
-        # one pinned staging buffer [pis | zs | stones]; torch's host allocator keeps the
-        # block alive until the copies queued from it have run
+        # one pinned staging buffer [pis | zs | stones], alive like _pinned's until its copies have run
         stage = torch.empty(n * (_PIX * 4 + 4 + _PIX), dtype=torch.uint8, pin_memory=True)
         o1, o2 = n * _PIX * 4, n * _PIX * 4 + n * 4
         h_pi = stage[:o1].view(torch.float32).view(n, _PIX)
         h_z = stage[o1:o2].view(torch.float32)
         h_st = stage[o2:].view(torch.int8).view(n, _PIX)
-        h_pi.numpy()[...] = P
-        h_z.numpy()[...] = Z
-        h_st.numpy()[...] = stones
         tail = (self.head + self.count) % self.cap_pos
-        first = min(n, self.cap_pos - tail)
-        for lo, hi, at in ((0, first, tail), (first, n, 0)):   # the write splits in two when it wraps
-            if hi > lo:
-                self.pis[at:at + hi - lo].copy_(h_pi[lo:hi], non_blocking=True)
-                self.zs[at:at + hi - lo].copy_(h_z[lo:hi], non_blocking=True)
-                self.stones[at:at + hi - lo].copy_(h_st[lo:hi], non_blocking=True)
+        for dst, host, values in ((self.pis, h_pi, P), (self.zs, h_z, Z), (self.stones, h_st, stones)):
+            host.numpy()[...] = values
+            self._write(dst, host, tail)
         if surprise is not None:
             self._ensure_weights()
             with torch.cuda.device(self.device):
@@ -191,20 +221,13 @@ class DeviceReplayBuffer:
                     ptr(surprise), 8 if surprise.dim() == 2 else 1, n, n_all, float(mix), ptr(self._wq), self.cap_pos,
                     tail, torch.cuda.current_stream(self.device).cuda_stream), self.lib)
         elif self._wq is not None:     # eviction takes the old weights with the old positions
-            self._wq[tail:tail + first].fill_(QUANTA)
-            self._wq[0:n - first].fill_(QUANTA)
+            self._fill(self._wq, tail, n, QUANTA)
         if policy_weight is not None:
             self._ensure_policy_weights()
-            h_pw = torch.empty(n, dtype=torch.float32, pin_memory=True)
-            h_pw.numpy()[...] = policy_weight
-            for lo, hi, at in ((0, first, tail), (first, n, 0)):
-                if hi > lo:
-                    self._pw[at:at + hi - lo].copy_(h_pw[lo:hi], non_blocking=True)
+            self._write(self._pw, _pinned(policy_weight, torch.float32), tail)
         elif self._pw is not None:     # eviction takes the old weights with the old positions
-            self._pw[tail:tail + first].fill_(1.0)
-            self._pw[0:n - first].fill_(1.0)
-        self._prefix_ok = False
-        self._avg_ok = False
+            self._fill(self._pw, tail, n, 1.0)
+        self._ring_moved()
         over = self.count + n - self.cap_pos
         if over > 0:
             self.head = (self.head + over) % self.cap_pos
@@ -215,8 +238,7 @@ class DeviceReplayBuffer:
         if self._wq is None:   # every position held so far weighs 1.0
             self._wq = torch.full((self.cap_pos,), QUANTA, dtype=torch.int32, device=self.device)
             self.weights = self._wq.view(torch.uint32)
-            self._prefix = torch.zeros(self.cap_pos, dtype=torch.int64, device=self.device)
-            self._prefix_ok = False
+            self._prefix = torch.zeros(self.cap_pos, dtype=torch.int64, device=self.device)   # not yet scanned
 
     def set_weights(self, w) -> None:
         """Weights of the positions held, a host float array [count] in ring order (oldest
@@ -230,20 +252,15 @@ class DeviceReplayBuffer:
         if not q.sum() > 0:
             raise ValueError("every weight rounds to zero quanta (one quantum is 2**-16)")
         self._ensure_weights()
-        stage = torch.empty(self.count, dtype=torch.int32, pin_memory=True)
-        stage.numpy()[...] = q
-        first = min(self.count, self.cap_pos - self.head)
-        self._wq[self.head:self.head + first].copy_(stage[:first], non_blocking=True)
-        self._wq[0:self.count - first].copy_(stage[first:], non_blocking=True)
-        self._prefix_ok = False
+        self._write(self._wq, _pinned(q, torch.int32), self.head)
+        self._weights_moved()
 
     def get_weights(self) -> np.ndarray:
         """The weights of the positions held, float64 [count] in ring order (all 1.0 for a
         buffer without weights).  Synchronises."""
         if self._wq is None:
             return np.ones(self.count, dtype=np.float64)
-        order = (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
-        return self._wq[order].cpu().numpy().astype(np.float64) / QUANTA
+        return self._wq[self._order()].cpu().numpy().astype(np.float64) / QUANTA
 
     def effective_sample_size(self) -> float:
         """(sum w)^2 / sum w^2 over the positions held: how many equally weighted positions
@@ -265,20 +282,15 @@ class DeviceReplayBuffer:
         if not np.isfinite(w).all() or (w < 0).any():
             raise ValueError("policy weights must be finite and >= 0")
         self._ensure_policy_weights()
-        stage = torch.empty(self.count, dtype=torch.float32, pin_memory=True)
-        stage.numpy()[...] = w
-        first = min(self.count, self.cap_pos - self.head)
-        self._pw[self.head:self.head + first].copy_(stage[:first], non_blocking=True)
-        self._pw[0:self.count - first].copy_(stage[first:], non_blocking=True)
-        self._avg_ok = False
+        self._write(self._pw, _pinned(w, torch.float32), self.head)
+        self._averaging_inputs_moved()
 
     def get_policy_weights(self) -> np.ndarray:
         """The policy loss weights of the positions held, float32 [count] in ring order (all
         1.0 for a buffer without them).  Synchronises."""
         if self._pw is None:
             return np.ones(self.count, dtype=np.float32)
-        order = (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
-        return self._pw[order].cpu().numpy()
+        return self._pw[self._order()].cpu().numpy()
 
     def _gather_policy_weight(self, d_ids, batch_size: int, st) -> torch.Tensor:
         """[B] float32: the policy weight of each image id's position, on the device (ones,
@@ -287,8 +299,8 @@ class DeviceReplayBuffer:
             return torch.ones(batch_size, dtype=torch.float32, device=self.device)
         vals = self._avg["pw_avg"] if self._avg_on else self._pw   # refreshed by the caller's _targets()
         w = torch.empty(batch_size, dtype=torch.float32, device=self.device)
-        check(self.lib.azg_pv_replay_gather_weight(ptr(vals), self.cap_pos, self.head, self.count, self.nsym,
-                                                   ptr(d_ids), batch_size, ptr(w), st), self.lib)
+        check(self.lib.azg_pv_replay_gather_weight(ptr(vals), *self._ring(), self.nsym, ptr(d_ids), batch_size, ptr(w),
+                                                   st), self.lib)
         return w
 
     # ------------------------------------------------------ position averaging
@@ -303,7 +315,7 @@ class DeviceReplayBuffer:
         on = bool(on)
         if on != self._avg_on:
             self._avg_on = on
-            self._avg_ok = False
+            self._averaging_inputs_moved()
 
     def _ensure_averages(self) -> None:
         if self._avg is None:
@@ -329,11 +341,11 @@ class DeviceReplayBuffer:
         n = self.count
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream(self.device).cuda_stream
-            check(self.lib.azg_pv_replay_canon_keys(ptr(self.stones), self.cap_pos, self.head, n, self.nsym,
-                                                    ptr(a["keys"]), ptr(a["syms"]), st), self.lib)
+            check(self.lib.azg_pv_replay_canon_keys(ptr(self.stones), *self._ring(), self.nsym, ptr(a["keys"]),
+                                                    ptr(a["syms"]), st), self.lib)
             keys_sorted, perm = torch.sort(a["keys"][:n], stable=True)   # equal keys adjacent, in ring order
             check(self.lib.azg_pv_replay_average(
-                ptr(self.stones), ptr(self.pis), ptr(self.zs), ptr(self._pw), self.cap_pos, self.head, n,
+                ptr(self.stones), ptr(self.pis), ptr(self.zs), ptr(self._pw), *self._ring(),
                 ptr(keys_sorted), ptr(perm), ptr(a["syms"]), ptr(a["pi_avg"]), ptr(a["z_avg"]),
                 ptr(a["pw_avg"]) if self._pw is not None else None, ptr(a["group_first"]), ptr(a["group_size"]), st),
                 self.lib)
@@ -375,8 +387,7 @@ class DeviceReplayBuffer:
         (None for a buffer without policy weights), "group_first", "group_size", "keys"
         (uint64), "syms".  Synchronises: for tests and inspection."""
         first = self._ring_order_int("group_first")
-        a, n = self._avg, self.count
-        order = (self.head + torch.arange(n, device=self.device)) % self.cap_pos
+        a, n, order = self._avg, self.count, self._order()
         return {"pi": a["pi_avg"][order].cpu().numpy(), "z": a["z_avg"][order].cpu().numpy(),
                 "policy_weight": a["pw_avg"][order].cpu().numpy() if self._avg_pw else None,
                 "group_first": first, "group_size": a["group_size"][:n].cpu().numpy(),
@@ -396,21 +407,21 @@ class DeviceReplayBuffer:
         if int(ids.min()) < 0 or int(ids.max()) >= len(self):
             raise ValueError(f"image id outside [0, {len(self)})")
         dev = self.device
-        h_ids = torch.empty(batch_size, dtype=torch.int64, pin_memory=True)
-        h_ids.numpy()[...] = ids
         with torch.cuda.device(dev):
-            d_ids = h_ids.to(dev, non_blocking=True)
-            s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
-            p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
-            z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
-            pis, zs = self._targets()
-            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(pis), ptr(zs), self.cap_pos,
-                                                self.head, self.count, self.nsym, ptr(d_ids), batch_size,
-                                                ptr(s), ptr(p), ptr(z),
-                                                torch.cuda.current_stream(dev).cuda_stream), self.lib)
-            if with_policy_weight:
-                return s, p, z, self._gather_policy_weight(d_ids, batch_size,
-                                                           torch.cuda.current_stream(dev).cuda_stream)
+            d_ids = _pinned(ids, torch.int64).to(dev, non_blocking=True)
+            return self._gather_batch(d_ids, batch_size, with_policy_weight, torch.cuda.current_stream(dev).cuda_stream)
+
+    def _gather_batch(self, d_ids, batch_size: int, with_policy_weight: bool, st):
+        """sample's and sample_weighted's tail: the batch of the device image ids d_ids, on stream st."""
+        dev = self.device
+        s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
+        p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
+        z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
+        pis, zs = self._targets()
+        check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(pis), ptr(zs), *self._ring(), self.nsym, ptr(d_ids),
+                                            batch_size, ptr(s), ptr(p), ptr(z), st), self.lib)
+        if with_policy_weight:
+            return s, p, z, self._gather_policy_weight(d_ids, batch_size, st)
         return s, p, z
 
     def draw_words(self, batch_size: int) -> np.ndarray:
@@ -433,29 +444,17 @@ class DeviceReplayBuffer:
         if rnd.dtype != np.uint64 or rnd.shape != (batch_size, 2):
             raise ValueError(f"rnd must be uint64 [{batch_size}, 2], got {rnd.dtype} {rnd.shape}")
         self._ensure_weights()
-        dev = self.device
-        h_rnd = torch.empty((batch_size, 2), dtype=torch.int64, pin_memory=True)
-        h_rnd.numpy()[...] = rnd.view(np.int64)
+        dev, h_rnd = self.device, _pinned(rnd.view(np.int64), torch.int64)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             if not self._prefix_ok:
-                check(self.lib.azg_pv_replay_prefix(ptr(self._wq), self.cap_pos, self.head, self.count,
-                                                    ptr(self._prefix), st), self.lib)
+                check(self.lib.azg_pv_replay_prefix(ptr(self._wq), *self._ring(), ptr(self._prefix), st), self.lib)
                 self._prefix_ok = True
             d_rnd = h_rnd.to(dev, non_blocking=True)
             d_ids = torch.empty(batch_size, dtype=torch.int64, device=dev)
             check(self.lib.azg_pv_replay_draw(ptr(self._prefix), self.count, self.nsym, ptr(d_rnd), batch_size,
                                               ptr(d_ids), st), self.lib)
-            s = torch.empty((batch_size, 3, _N, _N), dtype=torch.float32, device=dev)
-            p = torch.empty((batch_size, _PIX), dtype=torch.float32, device=dev)
-            z = torch.empty((batch_size, 1), dtype=torch.float32, device=dev)
-            pis, zs = self._targets()
-            check(self.lib.azg_pv_replay_gather(ptr(self.stones), ptr(pis), ptr(zs), self.cap_pos,
-                                                self.head, self.count, self.nsym, ptr(d_ids), batch_size,
-                                                ptr(s), ptr(p), ptr(z), st), self.lib)
-            if with_policy_weight:
-                return s, p, z, self._gather_policy_weight(d_ids, batch_size, st)
-        return s, p, z
+            return self._gather_batch(d_ids, batch_size, with_policy_weight, st)
 
     # ------------------------------------------------------------ host format
     def to_host(self) -> ReplayBuffer:
@@ -465,7 +464,7 @@ class DeviceReplayBuffer:
         out = ReplayBuffer(capacity=self.capacity)
         if not self.count:
             return out
-        order = (self.head + torch.arange(self.count, device=self.device)) % self.cap_pos
+        order = self._order()
         st = self.stones[order].cpu().numpy().reshape(self.count, _N, _N)
         P = self.pis[order].cpu().numpy()
         zs = [float(v) for v in self.zs[order].cpu().numpy()]

@@ -196,6 +196,14 @@ def _score_line(tag: str, d: Optional[dict]) -> str:
             f"total_loss={d['total_loss']:.6f} policy_top1={d['policy_top1']:.4f}")
 
 
+def _load_sidecar(path: str, count: int) -> Optional[np.ndarray]:
+    """Weights saved beside a buffer pickle of ``count`` positions, or None: no file, or another buffer's (length)."""
+    if not count or not os.path.exists(path):
+        return None
+    saved = np.load(path, allow_pickle=False)
+    return saved if saved.shape == (count,) else None
+
+
 def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterations: int = 5,
                     games_per_iteration: int = 8, n_simulations: int = 50, buffer_size: int = 10000,
                     batch_size: int = 128, epochs_per_iter: int = 2, temp_threshold: int = 8, eval_games: int = 12,
@@ -342,16 +350,17 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             buffer.set_target_averaging(True)
     else:
         buffer = load_replay_buffer(buffer_path, capacity=buffer_size) or ReplayBuffer(capacity=buffer_size)
-    weights_path = os.path.join(model_dir, f"replay_weights_latest{suffix}.npy")
-    if surprise_weight is not None and buffer.count and os.path.exists(weights_path):
-        saved = np.load(weights_path, allow_pickle=False)
-        if saved.shape == (buffer.count,):   # the sidecar of another buffer: start from 1.0 instead
-            buffer.set_weights(saved)
-    pweights_path = os.path.join(model_dir, f"replay_policy_weights_latest{suffix}.npy")
-    if playout_cap is not None and buffer.count and os.path.exists(pweights_path):
-        saved = np.load(pweights_path, allow_pickle=False)
-        if saved.shape == (buffer.count,):   # the sidecar of another buffer: start from 1.0 instead
-            buffer.set_policy_weights(saved)
+    sidecars = []   # (file, setter, getter) of the buffer's per-position weights in use, kept beside its pickle
+    if surprise_weight is not None:
+        sidecars.append((f"replay_weights_latest{suffix}.npy", buffer.set_weights, buffer.get_weights))
+    if playout_cap is not None:
+        sidecars.append((f"replay_policy_weights_latest{suffix}.npy", buffer.set_policy_weights, buffer.get_policy_weights))
+    for file, setter, _ in sidecars:
+        saved = _load_sidecar(os.path.join(model_dir, file), buffer.count)
+        if saved is not None:
+            setter(saved)
+    sample = buffer.sample if surprise_weight is None else buffer.sample_weighted
+    sample_kw = {} if playout_cap is None else {"with_policy_weight": True}
     # a device buffer of single images (nsym = 1: a loaded buffer that is not whole groups
     # of 8) takes the expanded examples like the deque; otherwise it forms the images itself
     host_symmetries = not device_buffer or buffer.nsym == 1
@@ -385,17 +394,14 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             score_before = _score_new_games(model_candidate, examples, score_max_examples)
             if main:
                 print(_score_line("before training", score_before))
-        if surprise_weight is not None and examples:
-            kl = _score_surprise(model_candidate, examples)
-            if pol_w is None:
-                buffer.add_positions(examples, surprise=kl, mix=surprise_weight)
-            else:   # a fast position's policy target is not trusted: no surprise, the uniform share only
-                kl = kl[:, 0] * torch.from_numpy((pol_w > 0).astype(np.float32)).to(kl.device)
-                buffer.add_positions(examples, surprise=kl, mix=surprise_weight, policy_weight=pol_w)
-        elif pol_w is not None:
-            buffer.add_positions(examples, policy_weight=pol_w)
-        elif device_buffer:
-            buffer.add_positions(examples)
+        if device_buffer:
+            add_kw = {} if pol_w is None else {"policy_weight": pol_w}
+            if surprise_weight is not None and examples:
+                kl = _score_surprise(model_candidate, examples)
+                if pol_w is not None:   # a fast position's policy target is not trusted: no surprise, the uniform share only
+                    kl = kl[:, 0] * torch.from_numpy((pol_w > 0).astype(np.float32)).to(kl.device)
+                add_kw.update(surprise=kl, mix=surprise_weight)
+            buffer.add_positions(examples, **add_kw)
         else:
             buffer.add(examples)
         t_sp = time.time() - t0
@@ -410,14 +416,10 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             for epoch in range(epochs_per_iter):
                 te = time.time()
                 for _ in range(n_batches):
-                    if playout_cap is not None:
-                        s, p, z, pw = (buffer.sample(batch_size, with_policy_weight=True) if surprise_weight is None
-                                       else buffer.sample_weighted(batch_size, with_policy_weight=True))
-                        loss_info = model_candidate.train_batch_device(s, p, z, epochs=1, policy_weight=pw)
-                        continue
-                    s, p, z = (buffer.sample(batch_size) if surprise_weight is None
-                               else buffer.sample_weighted(batch_size))
-                    if device_buffer:   # the synchronous step: a skipped step is redone as on the host path
+                    s, p, z, *pw = sample(batch_size, **sample_kw)
+                    if pw:   # playout cap: the batch comes with its policy loss weights
+                        loss_info = model_candidate.train_batch_device(s, p, z, epochs=1, policy_weight=pw[0])
+                    elif device_buffer:   # the synchronous step: a skipped step is redone as on the host path
                         loss_info = model_candidate.train_batch_device(s, p, z, epochs=1)
                     else:
                         loss_info = model_candidate.train_batch(s, p, z, epochs=1)
@@ -475,10 +477,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             model_best.save(path)
             print(f" saved snapshot: {path}")
         save_replay_buffer(buffer.to_host() if device_buffer else buffer, buffer_path)
-        if surprise_weight is not None:
-            np.save(weights_path, buffer.get_weights())
-        if playout_cap is not None:
-            np.save(pweights_path, buffer.get_policy_weights())
+        for file, _, getter in sidecars:
+            np.save(os.path.join(model_dir, file), getter())
         if main:
             print(f"iteration {it} done in {(time.time() - t0) / 60:.2f} min; winners {winners}")
     if main:

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import has_gpu
+from replay_helpers import synthetic_positions
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
 
@@ -22,16 +23,7 @@ DEV = "cuda:0"
 
 def _positions(n, seed):
     """n canonical examples (state [3,15,15], pi [225], z) with pairwise distinct images."""
-    from mcts.new_mcts_alpha import MCTS
-    from oracle.boards import encode_batch, synth_positions, synth_targets
-    boards, players = synth_positions(n, seed=seed)
-    states = encode_batch(boards, players)
-    pi, z = synth_targets(n, seed=seed + 1)
-    out = [(states[i], pi[i], float(z[i, 0])) for i in range(n)]
-    for s, p, _ in out:   # the inputs can tell the 8 images apart, in the state AND in pi
-        imgs = MCTS.symmetries(None, s, p)
-        assert len({si.tobytes() for si, _ in imgs}) == 8 and len({pi_.tobytes() for _, pi_ in imgs}) == 8
-    return out
+    return synthetic_positions(n, seed, distinct_images=True)
 
 
 def _expand(examples):

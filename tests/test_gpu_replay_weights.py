@@ -13,6 +13,7 @@ import torch
 
 import replay_weights_reference as ref
 from conftest import has_gpu
+from replay_helpers import synthetic_positions
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
 
@@ -188,17 +189,9 @@ def test_draw_is_exactly_proportional():
 
 
 # ---------------------------------------------------------------------- the buffer's API
-def _positions(n, seed):
-    from oracle.boards import encode_batch, synth_positions, synth_targets
-    boards, players = synth_positions(n, seed=seed)
-    states = encode_batch(boards, players)
-    pi, z = synth_targets(n, seed=seed + 1)
-    return [(states[i], pi[i], float(z[i, 0])) for i in range(n)]
-
-
 @pytest.fixture(scope="module")
 def positions():
-    return _positions(12, seed=301)
+    return synthetic_positions(12, seed=301)
 
 
 def _same(a, b):
@@ -285,6 +278,30 @@ def test_set_weights_and_eviction_follow_a_host_model(positions):
         with pytest.raises(ValueError):
             dev.set_weights(bad)
     assert np.array_equal(dev.get_weights(), np.rint(w * QUANTA) / QUANTA)
+
+
+def test_every_per_slot_array_wraps_at_the_same_place(positions):
+    """One wrapped write, five per-slot arrays: position k of a batch of 4 added behind 3 in a ring of
+    5 slots is in slot (3 + k) % 5 of stones, pis, zs, _wq and _pw alike, bit for bit."""
+    from replay import DeviceReplayBuffer
+    dev = DeviceReplayBuffer(40, DEV)
+    assert dev.cap_pos == 5 and dev.nsym == 8
+    dev.add_positions(positions[:3])
+    new = positions[3:7]
+    s = np.array([0.3, 0.0, 2.5, 0.9], dtype=np.float32)
+    pw = np.array([1.0, 0.0, 0.5, 2.0], dtype=np.float32)
+    dev.add_positions(new, surprise=s, mix=0.75, policy_weight=pw)
+    assert dev.head == 2 and dev.count == 5
+    q = ref.surprise_quanta(s, 0.75)
+    stones, pis, zs, wq, pws = (t.cpu().numpy() for t in (dev.stones, dev.pis, dev.zs, dev._wq, dev._pw))
+    for k, (state, pi, z) in enumerate(new):
+        slot = (3 + k) % 5
+        assert np.array_equal(stones[slot], (state[0] + 2 * state[1]).astype(np.int8).reshape(-1))
+        assert np.array_equal(pis[slot].view(np.uint32), np.asarray(pi, dtype=np.float32).view(np.uint32))
+        assert zs[slot:slot + 1].view(np.uint32)[0] == np.array([z], dtype=np.float32).view(np.uint32)[0]
+        assert int(wq[slot]) == int(q[k])
+        assert pws[slot:slot + 1].view(np.uint32)[0] == pw[k:k + 1].view(np.uint32)[0]
+    assert int(wq[2]) == QUANTA and pws[2] == 1.0   # the survivor of the first three: slot 2, the new head
 
 
 # ----------------------------------------------------------------------------- the loop
