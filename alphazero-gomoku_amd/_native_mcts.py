@@ -12,6 +12,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AZG_MCTS_LIB", os.path.join(_HERE, "libazg_mcts.so"))
 
 IDLE, NEED_EVAL, DONE = 0, 1, 2
+# search="reference": the reference's search bit for bit, which never reads the net's value;
+# search="alphazero": value backup under virtual loss (AZG_MCTS_SEARCH_VALUE in azg_mcts.h)
+SEARCH_MODES = {"reference": 0, "alphazero": 1}
+
+
+def search_mode(search) -> int:
+    """The C-ABI mode of a ``search=`` keyword; ValueError on anything else."""
+    if not isinstance(search, str) or search not in SEARCH_MODES:
+        raise ValueError(f"search must be one of {sorted(SEARCH_MODES)}, got {search!r}")
+    return SEARCH_MODES[search]
 
 
 class MctsConfig(ctypes.Structure):
@@ -35,6 +45,12 @@ _SIGS = {
     "azg_mcts_noise_request": (_I32, [_P, _I32, _P]),
     "azg_mcts_set_root_prior": (_I32, [_P, _I32, _P]),
     "azg_mcts_get_pi": (_I32, [_P, _I32, _P]),
+    "azg_mcts_set_search_mode": (_I32, [_P, _I32]),
+    "azg_mcts_get_search_mode": (_I32, [_P]),
+    "azg_mcts_get_root_value": (_I32, [_P, _I32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float),
+                                       ctypes.POINTER(ctypes.c_int64)]),
+    "azg_mcts_inflight": (ctypes.c_int64, [_P, _I32]),
+    "azg_mcts_collisions": (ctypes.c_int64, [_P, _I32]),
     "azg_mcts_clear": (_I32, [_P, _I32]),
     "azg_mcts_tree_size": (ctypes.c_int64, [_P, _I32]),
     "azg_mcts_replay": (_I32, [_I32, _I32, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
@@ -75,7 +91,10 @@ class SearchForest:
 
     def __init__(self, n_games: int, n_simulations: int, rules: int = 0, board: int = 15, cpuct: float = 1.0,
                  batch_size: int = 32, dirichlet_alpha: float = 0.03, epsilon: float = 0.03,
-                 apply_dirichlet_n_first_moves: int = 10, add_dirichlet_noise: bool = True, n_threads: int = 0):
+                 apply_dirichlet_n_first_moves: int = 10, add_dirichlet_noise: bool = True, n_threads: int = 0,
+                 search: str = "reference"):
+        mode = search_mode(search)
+        self.search = search
         self.lib = load_library()
         self.n_games = int(n_games)
         self.board = int(board)
@@ -87,6 +106,8 @@ class SearchForest:
                               float(dirichlet_alpha), float(epsilon))
         self.h = _P()
         _check(self.lib.azg_mcts_create(ctypes.byref(self.cfg), self.n_games, ctypes.byref(self.h)))
+        if mode:   # the default makes no call: a forest that never asks is the reference search
+            self.set_search_mode(mode)
         self._leaves = None
         self.counts = np.zeros(self.n_games, np.int32)
         self.status = np.zeros(self.n_games, np.int32)
@@ -112,6 +133,29 @@ class SearchForest:
         caps = getattr(game, "captures", None) or {1: 0, 2: 0}
         _check(self.lib.azg_mcts_set_root(self.h, g, _addr(board), int(game.current_player), lr, lc,
                                           int(caps[1]), int(caps[2]), int(move_number)))
+
+    def set_search_mode(self, mode: int) -> None:
+        """azg_mcts_set_search_mode: 0 reference, 1 value search; only with every tree empty and
+        no search in progress."""
+        _check(self.lib.azg_mcts_set_search_mode(self.h, int(mode)))
+
+    def get_search_mode(self) -> int:
+        return int(self.lib.azg_mcts_get_search_mode(self.h))
+
+    def root_value(self, g: int):
+        """(q, v_net, visits) of slot g's root: q = sum(W)/sum(N) over its actions from the
+        root mover's view (0.0 without visits), the net's value of the root, sum(N)."""
+        q, v, n = ctypes.c_double(0.0), ctypes.c_float(0.0), ctypes.c_int64(0)
+        _check(self.lib.azg_mcts_get_root_value(self.h, g, ctypes.byref(q), ctypes.byref(v), ctypes.byref(n)))
+        return q.value, v.value, n.value
+
+    def inflight(self, g: int) -> int:
+        """Test hook: the sum of slot g's in-flight counters (virtual losses)."""
+        return int(self.lib.azg_mcts_inflight(self.h, g))
+
+    def collisions(self, g: int) -> int:
+        """Simulations of slot g that met a queued leaf (early emits) since its last clear."""
+        return int(self.lib.azg_mcts_collisions(self.h, g))
 
     def set_budget(self, g: int, n_simulations: int = -1, root_noise: int = -1) -> None:
         """Slot g's simulation budget and whether its root may get Dirichlet noise, from the

@@ -13,6 +13,13 @@
 //     installed, continues descending from the now-evaluated node;
 //   * installing resets N/W and overwrites the prior of every queued key.
 // Build with -ffp-contract=off (no FMA contraction: numpy rounds every op).
+//
+// The above is search mode AZG_MCTS_SEARCH_REFERENCE, the default.  It never reads the
+// network's value.  AZG_MCTS_SEARCH_VALUE (azg_mcts_set_search_mode; specified in
+// include/azg_mcts.h) is the AlphaZero search: the value is backed up, pending leaves put
+// a virtual loss on their path.  It has its own selection, descent and backup
+// (choose_value, run_game_value, feed_value) and shares only the rules, the tree storage
+// and the prior installation with the reference mode, whose code paths it does not touch.
 #include "../../include/azg_mcts.h"
 
 #include <omp.h>
@@ -171,9 +178,18 @@ struct Node {
     std::array<float, MAXN> P{};
     std::unique_ptr<std::array<double, MAXN>> P64;   // float64 prior (Dirichlet-mixed root)
     std::array<int32_t, MAXN> N{};
-    std::array<int32_t, MAXN> W{};
+    std::array<int32_t, MAXN> W{};   // value mode: the same slots hold float32 bits (wf / set_wf)
+    std::array<uint16_t, MAXN> O{};  // value mode: simulations in flight through the edge (virtual loss)
     std::array<uint8_t, MAXN> valid{};
     float V = 0.f;
+
+    float wf(int a) const
+    {
+        float f;
+        std::memcpy(&f, &W[a], sizeof(f));
+        return f;
+    }
+    void set_wf(int a, float f) { std::memcpy(&W[a], &f, sizeof(f)); }
 };
 
 // Node storage in fixed chunks: growing never moves a node.  (A std::vector<Node>
@@ -181,7 +197,7 @@ struct Node {
 // and the trees of one forest cross the doubling sizes in the same round -- the
 // self-play timeline showed 140-340 ms stalls of one advance call at those rounds.)
 class NodeStore {
-    static constexpr int kShift = 8, kChunk = 1 << kShift;   // 256 nodes (~750 KB) per chunk
+    static constexpr int kShift = 8, kChunk = 1 << kShift;   // 256 nodes (~870 KB) per chunk
     std::vector<std::unique_ptr<Node[]>> chunks_;
     size_t n_ = 0;
 
@@ -196,9 +212,12 @@ public:
     }
 };
 
+using Path = std::vector<std::pair<int32_t, int32_t>>;   // (node, action) from the root down
+
 struct Pending {
     Key key;
     State st;
+    Path path;   // value mode: the one simulation that waits for this leaf
 };
 
 struct GameSearch {
@@ -215,7 +234,7 @@ struct GameSearch {
     bool suspended = false;
     State cur;
     Key cur_key;
-    std::vector<std::pair<int32_t, int32_t>> path;
+    Path path;
     // leaf queue
     std::vector<Pending> queue;
     bool final_flush = false;
@@ -224,6 +243,17 @@ struct GameSearch {
     // noise hand-off
     bool noise_pending = false;
     int32_t noise_node = -1;
+    // value mode: the node that holds the last mixed root prior (dropped at the next set_root),
+    // and how often a simulation met a queued leaf and forced an early emit
+    int32_t mixed_node = -1;
+    int64_t collisions = 0;
+
+    bool queued(const Key& k) const
+    {
+        for (const Pending& pd : queue)
+            if (pd.key == k) return true;
+        return false;
+    }
 
     int32_t node_for(const Key& k) const
     {
@@ -255,6 +285,7 @@ struct azg_mcts {
     int A = 225;
     std::vector<GameSearch> games;
     std::vector<SlotBudget> budget;
+    int32_t mode = AZG_MCTS_SEARCH_REFERENCE;
 };
 
 namespace {
@@ -399,6 +430,109 @@ void run_game(const azg_mcts* h, GameSearch& gs)
     gs.status = AZG_MCTS_NEED_EVAL;   // the queue is emitted by the caller (advance_impl)
 }
 
+// ---- value mode (AZG_MCTS_SEARCH_VALUE; the rules are spelled out in include/azg_mcts.h) ----
+
+// PUCT over N + O visits with the in-flight ones counted as losses, all in float64.
+int choose_value(const azg_mcts* h, const Node& nd)
+{
+    const int A = h->A;
+    int64_t S = 0;
+    for (int i = 0; i < A; ++i)
+        if (nd.valid[i] == 1) S += (int64_t)nd.N[i] + nd.O[i];
+    const double sq = std::sqrt((double)(1 + S));
+    const double cp = h->cfg.cpuct;
+    int best = -1;
+    double bv = 0.0;
+    for (int i = 0; i < A; ++i) {
+        if (nd.valid[i] != 1) continue;
+        const int64_t n = (int64_t)nd.N[i] + nd.O[i];
+        const double w = (double)nd.wf(i) - (double)nd.O[i];
+        const double q = n > 0 ? w / (double)n : 0.0;
+        const double p = nd.P64 ? (*nd.P64)[i] : (double)nd.P[i];
+        double u = cp * p;
+        u = u * sq;
+        u = u / (double)(1 + n);
+        const double s = q + u;
+        if (best < 0 || s > bv) { bv = s; best = i; }
+    }
+    return best < 0 ? 0 : best;   // (a node always has a valid action: a full board is terminal)
+}
+
+// x is the value from the view of the side to move below the path's last edge
+void backup_value(GameSearch& gs, const Path& path, float x)
+{
+    for (int i = (int)path.size() - 1; i >= 0; --i) {
+        x = -x;
+        Node& nd = gs.nodes[path[i].first];
+        const int a = path[i].second;
+        nd.set_wf(a, nd.wf(a) + x);
+        nd.N[a] += 1;
+    }
+}
+
+void run_game_value(const azg_mcts* h, GameSearch& gs)
+{
+    const int bs = h->cfg.batch_size;
+    if (!gs.active) { gs.status = AZG_MCTS_IDLE; return; }
+    for (;;) {
+        if (!gs.in_sim) {
+            if (gs.sims_left == 0) {
+                if (!gs.queue.empty()) break;   // final flush; its feed empties the queue
+                gs.status = AZG_MCTS_DONE;
+                gs.active = false;
+                return;
+            }
+            gs.sims_left -= 1;
+            gs.in_sim = true;
+            gs.suspended = false;
+            gs.cur = gs.root;
+            gs.path.clear();
+        }
+        bool emit = false;
+        for (;;) {
+            Key k;
+            if (gs.suspended) {   // resume at the leaf this simulation collided with: now a node
+                k = gs.cur_key;
+                gs.suspended = false;
+            } else {
+                k = gs.cur.key();
+                if (gs.cur.game_over()) {
+                    backup_value(gs, gs.path, gs.cur.winner() == 0 ? 0.f : -1.f);
+                    gs.in_sim = false;
+                    break;
+                }
+                if (gs.node_for(k) < 0) {
+                    if (gs.queued(k)) {   // collision: wait here, without virtual loss, for the feed
+                        gs.suspended = true;
+                        gs.cur_key = k;
+                        gs.collisions += 1;
+                        emit = true;
+                        break;
+                    }
+                    for (const auto& e : gs.path) gs.nodes[e.first].O[e.second] += 1;
+                    gs.queue.push_back(Pending{k, gs.cur, gs.path});
+                    gs.in_sim = false;
+                    emit = (int)gs.queue.size() >= bs;
+                    break;
+                }
+            }
+            const int32_t id = gs.node_for(k);
+            const int a = choose_value(h, gs.nodes[id]);
+            gs.path.emplace_back(id, a);
+            gs.cur.do_move(a);
+        }
+        if (emit) break;
+    }
+    gs.status = AZG_MCTS_NEED_EVAL;
+}
+
+// After a pending leaf's node was installed: take its path's virtual loss back, back its value up.
+void feed_value(GameSearch& gs, const Pending& pd, float v)
+{
+    for (const auto& e : pd.path) gs.nodes[e.first].O[e.second] -= 1;
+    backup_value(gs, pd.path, v);
+}
+
 // Run all games (parallel), then write the pending leaves of every game, in game
 // order, either as float32 planes or as int8 boards + side to move (parallel copy
 // at prefix offsets).
@@ -416,7 +550,10 @@ int32_t advance_impl(azg_mcts* h, float* leaves, int8_t* boards, int8_t* players
         for (int g = 0; g < G; ++g) {
             GameSearch& gs = h->games[g];
             if (gs.status == AZG_MCTS_NEED_EVAL) continue;   // not fed yet: re-emit the same leaves
-            run_game(h, gs);
+            if (h->mode == AZG_MCTS_SEARCH_VALUE)
+                run_game_value(h, gs);
+            else
+                run_game(h, gs);
         }
 #pragma omp single
         {
@@ -503,6 +640,17 @@ int32_t azg_mcts_set_root(azg_mcts* h, int32_t g, const int8_t* board, int32_t p
     gs.path.clear();
     gs.active = true;
     gs.status = AZG_MCTS_IDLE;
+    if (h->mode == AZG_MCTS_SEARCH_VALUE) {
+        // the noise condition holds at every noisy move: a root that is already in the tree
+        // asks for its mix now, from its clean float32 prior
+        if (gs.mixed_node >= 0) gs.nodes[gs.mixed_node].P64.reset();
+        gs.mixed_node = -1;
+        const int32_t id = gs.node_for(gs.root_key);
+        if (id >= 0 && gs.noise_ok && move_number < h->cfg.apply_dirichlet_n_first_moves) {
+            gs.noise_pending = true;
+            gs.noise_node = id;
+        }
+    }
     return 0;
 }
 
@@ -559,6 +707,10 @@ int32_t azg_mcts_feed(azg_mcts* h, const float* probs, const float* values)
                 gs.noise_pending = true;
                 gs.noise_node = gs.node_for(pd.key);
             }
+            if (h->mode == AZG_MCTS_SEARCH_VALUE) {
+                nd.O.fill(0);
+                feed_value(gs, pd, nd.V);
+            }
         }
         gs.queue.clear();
         gs.status = AZG_MCTS_IDLE;
@@ -583,6 +735,7 @@ int32_t azg_mcts_set_root_prior(azg_mcts* h, int32_t g, const double* p64)
     Node& nd = gs.nodes[gs.noise_node];
     nd.P64.reset(new std::array<double, MAXN>());
     std::memcpy(nd.P64->data(), p64, sizeof(double) * h->A);
+    if (h->mode == AZG_MCTS_SEARCH_VALUE) gs.mixed_node = gs.noise_node;
     gs.noise_pending = false;
     gs.noise_node = -1;
     return 0;
@@ -608,6 +761,62 @@ int32_t azg_mcts_get_pi(azg_mcts* h, int32_t g, float* pi)
         for (int a = 0; a < A; ++a) pi[a] = v[a] / s;
     }
     return 0;
+}
+
+int32_t azg_mcts_set_search_mode(azg_mcts* h, int32_t mode)
+{
+    if (!h) return fail("azg_mcts_set_search_mode: bad arguments");
+    if (mode != AZG_MCTS_SEARCH_REFERENCE && mode != AZG_MCTS_SEARCH_VALUE)
+        return fail("azg_mcts_set_search_mode: unknown mode " + std::to_string(mode) +
+                    " (0 = reference, 1 = value)");
+    for (const GameSearch& gs : h->games) {
+        if (gs.active || gs.status == AZG_MCTS_NEED_EVAL)
+            return fail("azg_mcts_set_search_mode: a search is in progress");
+        if (gs.nodes.size() > 0)
+            return fail("azg_mcts_set_search_mode: a tree is not empty (azg_mcts_clear every game first)");
+    }
+    if (mode == AZG_MCTS_SEARCH_VALUE && h->cfg.batch_size > 65535)
+        return fail("azg_mcts_set_search_mode: the value search counts at most 65535 simulations in flight per "
+                    "edge (batch_size too large)");
+    h->mode = mode;
+    return 0;
+}
+
+int32_t azg_mcts_get_search_mode(const azg_mcts* h) { return h ? h->mode : -1; }
+
+int32_t azg_mcts_get_root_value(azg_mcts* h, int32_t g, double* q, float* v_net, int64_t* visits)
+{
+    if (!h || g < 0 || g >= (int)h->games.size()) return fail("azg_mcts_get_root_value: bad arguments");
+    const GameSearch& gs = h->games[g];
+    const int32_t id = gs.node_for(gs.root_key);
+    if (id < 0) return fail("azg_mcts_get_root_value: root not in tree");
+    const Node& nd = gs.nodes[id];
+    double w = 0.0;
+    int64_t n = 0;
+    for (int a = 0; a < h->A; ++a) {
+        w += h->mode == AZG_MCTS_SEARCH_VALUE ? (double)nd.wf(a) : (double)nd.W[a];
+        n += nd.N[a];
+    }
+    if (q) *q = n > 0 ? w / (double)n : 0.0;
+    if (v_net) *v_net = nd.V;
+    if (visits) *visits = n;
+    return 0;
+}
+
+int64_t azg_mcts_inflight(const azg_mcts* h, int32_t g)
+{
+    if (!h || g < 0 || g >= (int)h->games.size()) return -1;
+    const GameSearch& gs = h->games[g];
+    int64_t s = 0;
+    for (size_t i = 0; i < gs.nodes.size(); ++i)
+        for (int a = 0; a < h->A; ++a) s += gs.nodes[i].O[a];
+    return s;
+}
+
+int64_t azg_mcts_collisions(const azg_mcts* h, int32_t g)
+{
+    if (!h || g < 0 || g >= (int)h->games.size()) return -1;
+    return h->games[g].collisions;
 }
 
 int32_t azg_mcts_clear(azg_mcts* h, int32_t g)

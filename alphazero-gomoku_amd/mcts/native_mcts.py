@@ -16,6 +16,12 @@ them.  Each game owns a ``numpy.random.RandomState`` (Dirichlet noise and move
 sampling), so a game's result does not depend on which other games share its
 batches or on thread scheduling -- it equals that game played alone through the
 reference-semantics Python search with the same RandomState.
+
+Every class here takes ``search="reference" | "alphazero"``.  "reference", the default,
+is the reference's search bit for bit, and like it never reads the value head: the net's
+value is stored and only terminal outcomes are backed up.  "alphazero" backs the value of
+every evaluated leaf up under virtual loss and re-mixes root noise at every noisy move
+(include/azg_mcts.h has the rules).  It is host code over the same forward: no new kernel.
 """
 from __future__ import annotations
 
@@ -45,7 +51,9 @@ class NativeMCTS:
     drive = _PyMCTS.drive
 
     def __init__(self, game_class, n_simulations, nn_model, cpuct=1.0, batch_size=32, dirichlet_alpha=0.03,
-                 epsilon=0.03, apply_dirichlet_n_first_moves=10, add_dirichlet_noise=True, rng=None, n_threads=1):
+                 epsilon=0.03, apply_dirichlet_n_first_moves=10, add_dirichlet_noise=True, rng=None, n_threads=1,
+                 search="reference"):
+        self.search = search
         self.game_class = game_class
         self.n_simulations = n_simulations
         self.nn_model = nn_model
@@ -61,7 +69,7 @@ class NativeMCTS:
         self.forest = SearchForest(1, n_simulations, rules=_rules_of(game_class), board=g0.size, cpuct=cpuct,
                                    batch_size=batch_size, dirichlet_alpha=dirichlet_alpha, epsilon=epsilon,
                                    apply_dirichlet_n_first_moves=apply_dirichlet_n_first_moves,
-                                   add_dirichlet_noise=add_dirichlet_noise, n_threads=n_threads)
+                                   add_dirichlet_noise=add_dirichlet_noise, n_threads=n_threads, search=search)
 
     def clear_tree(self):
         self.forest.clear(0)
@@ -69,21 +77,29 @@ class NativeMCTS:
     def tree_size(self) -> int:
         return self.forest.tree_size(0)
 
+    def root_value(self):
+        """(q, v_net, visits) of the last searched root (SearchForest.root_value)."""
+        return self.forest.root_value(0)
+
     def run(self, game_state, move_number):
         return self.drive(self.run_gen(game_state, move_number))
+
+    def _mix_root(self):
+        p32 = self.forest.noise_request(0)
+        if p32 is not None:
+            self.forest.set_root_prior(0, _mix_noise(p32, self.rng, self.dirichlet_alpha, self.epsilon))
 
     def run_gen(self, game_state, move_number):
         f = self.forest
         f.set_root(0, game_state, move_number)
+        self._mix_root()   # "alphazero": a root already in the tree is mixed anew; "reference": never pending here
         while True:
             n = f.advance()
             if f.status[0] != NEED_EVAL:
                 break
             probs, values = yield f.leaves[:n].copy()
             f.feed(probs, values)
-            p32 = f.noise_request(0)
-            if p32 is not None:
-                f.set_root_prior(0, _mix_noise(p32, self.rng, self.dirichlet_alpha, self.epsilon))
+            self._mix_root()
         return f.get_pi(0)
 
 
@@ -132,7 +148,8 @@ class NativeSelfPlay:
         the GPU evaluates another (leaves cross PCIe as int8 boards, encoded on the GPU).
     Every game draws from its own RandomState, so results are identical in both modes
     and for any grouping.  Statistics: boards, forwards, nn_seconds (host time waiting
-    for / inside evaluation), search_seconds, max_batch.
+    for / inside evaluation), search_seconds, max_batch, emits (how many times a game handed
+    leaves to a forward).
 
     ``playout_cap=(p_full, fast_sims)`` turns on KataGo's playout cap randomization: before
     each move a game flips a coin from a stream of its own, RandomState((seed + 0x9E3779B1)
@@ -148,7 +165,9 @@ class NativeSelfPlay:
     def __init__(self, evaluate: Optional[Callable], game_class, n_games: int, n_simulations: int,
                  cpuct: float = 1.0, batch_size: int = 32, dirichlet_alpha: float = 0.03, epsilon: float = 0.03,
                  apply_dirichlet_n_first_moves: int = 10, add_dirichlet_noise: bool = True, n_threads: int = 0,
-                 evaluator_factory: Optional[Callable] = None, groups: int = 2, playout_cap=None):
+                 evaluator_factory: Optional[Callable] = None, groups: int = 2, playout_cap=None,
+                 search: str = "reference"):
+        self.search = search
         if (evaluate is None) == (evaluator_factory is None):
             raise ValueError("give exactly one of evaluate / evaluator_factory")
         if playout_cap is not None:
@@ -171,7 +190,7 @@ class NativeSelfPlay:
             f = SearchForest(hi - lo, n_simulations, rules=_rules_of(game_class), board=g0.size, cpuct=cpuct,
                              batch_size=batch_size, dirichlet_alpha=dirichlet_alpha, epsilon=epsilon,
                              apply_dirichlet_n_first_moves=apply_dirichlet_n_first_moves,
-                             add_dirichlet_noise=add_dirichlet_noise, n_threads=n_threads)
+                             add_dirichlet_noise=add_dirichlet_noise, n_threads=n_threads, search=search)
             self.forests.append(f)
             if evaluate is not None:
                 self.evals.append(PlanesEvaluator(evaluate, f))
@@ -179,6 +198,7 @@ class NativeSelfPlay:
                 self.evals.append(_BoardsAdapter(evaluator_factory((hi - lo) * batch_size), f))
         self.forest = self.forests[0]
         self.boards = self.forwards = self.max_batch = 0
+        self.emits = 0          # (game, advance) pairs that emitted leaves: boards / emits = leaves per game per advance
         self.moves = self.rounds = 0
         self.game_lengths: List[int] = []
         self.nn_seconds = self.search_seconds = 0.0
@@ -212,7 +232,7 @@ class NativeSelfPlay:
             f = self.forests[k]
             for g in range(lo, hi):
                 f.clear(g - lo)          # a fresh tree per game, reused across its moves
-                self._start_move(f, g - lo, g, games[g], coins, full)
+                self._start_move(f, g - lo, g, games[g], coins, full, rngs)
             live[k] = hi - lo
         pending = [False] * len(self.forests)
         while any(live) or any(pending):
@@ -254,6 +274,7 @@ class NativeSelfPlay:
                         pending[k] = True
                         self.boards += n
                         self.forwards += 1
+                        self.emits += int(np.count_nonzero(f.counts))
                         self.max_batch = max(self.max_batch, n)
                     self._play_done(f, done, lo, games, hist, moves, results, live, k, rngs, temp_fn, max_moves,
                                     use_symmetries, coins, full)
@@ -263,9 +284,11 @@ class NativeSelfPlay:
         self.rounds = max(self.rounds, max(moves) if moves else 0)
         return results
 
-    def _start_move(self, f, i, g, game, coins, full):
+    def _start_move(self, f, i, g, game, coins, full, rngs):
         """Start the search of game g's next move (slot i of forest f), under the playout cap
-        with the budget its coin decides."""
+        with the budget its coin decides.  Under search="alphazero" a root that is already in
+        the tree asks for its noise mix here; under "reference" the request is never pending
+        at this point, so nothing is drawn."""
         if coins is not None:
             p_full, fast_sims = self.playout_cap
             full[g] = bool(coins[g].random_sample() < p_full)
@@ -276,6 +299,9 @@ class NativeSelfPlay:
                 f.set_budget(i, fast_sims, 0)
                 self.fast_moves += 1
         f.set_root(i, game, len(game.move_history))
+        p32 = f.noise_request(i)
+        if p32 is not None:
+            f.set_root_prior(i, _mix_noise(p32, rngs[g], self.alpha, self.eps))
 
     def _play_done(self, f, done, lo, games, hist, moves, results, live, k, rngs, temp_fn, max_moves,
                    use_symmetries, coins=None, full=None):
@@ -302,7 +328,7 @@ class NativeSelfPlay:
                 self.game_lengths.append(moves[g])
                 live[k] -= 1
             else:
-                self._start_move(f, i, g, game, coins, full)
+                self._start_move(f, i, g, game, coins, full, rngs)
 
     @staticmethod
     def _finish(history, winner, use_symmetries):
@@ -344,14 +370,23 @@ class NativeEval:
     evaluators (PyTorchModel.board_evaluator): the leaves leave the search as int8
     boards, are encoded on the GPU, both networks' batches are submitted before
     either is waited on, and the masked priors come back (same results: the
-    search's own masking of an already-masked prior is the identity)."""
+    search's own masking of an already-masked prior is the identity).
+
+    ``search``: one mode for both networks, or {tag: mode} -- every tag owns its forest, so
+    one net can play itself under the two searches."""
 
     def __init__(self, evaluators: Optional[dict], game_class, n_games: int, n_simulations: int,
                  cpuct: float = 1.0, batch_size: int = 32, n_threads: int = 0,
-                 evaluator_factories: Optional[dict] = None):
+                 evaluator_factories: Optional[dict] = None, search="reference"):
         if (evaluators is None) == (evaluator_factories is None):
             raise ValueError("give exactly one of evaluators / evaluator_factories")
         self.tags = list(evaluators if evaluators is not None else evaluator_factories)
+        if isinstance(search, dict):
+            if set(search) != set(self.tags):
+                raise ValueError(f"search must name every tag of {self.tags}, got {sorted(search)}")
+            self.search = dict(search)
+        else:
+            self.search = {t: search for t in self.tags}
         self.evaluators = evaluators
         self.boards_ev = None if evaluator_factories is None else \
             {t: f(n_games * batch_size) for t, f in evaluator_factories.items()}
@@ -359,7 +394,7 @@ class NativeEval:
         g0 = game_class()
         self.forests = {t: SearchForest(n_games, n_simulations, rules=_rules_of(game_class), board=g0.size,
                                         cpuct=cpuct, batch_size=batch_size, add_dirichlet_noise=False,
-                                        n_threads=n_threads) for t in self.tags}
+                                        n_threads=n_threads, search=self.search[t]) for t in self.tags}
         self.boards = self.forwards = self.max_batch = 0
         self.nn_seconds = self.search_seconds = 0.0
 

@@ -22,7 +22,8 @@ from mcts.native_mcts import NativeMCTS
 
 class AlphaPlayer:
     def __init__(self, rules="gomoku", board_size=15, n_simulations=5000, c_puct=1.0, model_path=None,
-                 nn_model=None, mcts_kwargs=None, mcts_class=None, leaf_symmetry=None, eval_precision=None):
+                 nn_model=None, mcts_kwargs=None, mcts_class=None, leaf_symmetry=None, eval_precision=None,
+                 search=None):
         if nn_model is None:
             from network import PyTorchModel
             nn_model = PyTorchModel
@@ -49,8 +50,15 @@ class AlphaPlayer:
         # leaf_symmetry (None, an int 0..7, "random" or "mean8"): the search's leaves are
         # evaluated under board symmetries (network.SymmetricModel)
         search_net = self.net if leaf_symmetry is None else self.net.symmetric(leaf_symmetry)
+        # search (None, "reference" or "alphazero"; also through mcts_kwargs): the native
+        # search's mode.  The default, "reference", never reads the value head; "alphazero"
+        # backs the net's value up under virtual loss.  None passes no keyword, so another
+        # mcts_class with the reference's constructor still works.
+        mcts_kwargs = dict(mcts_kwargs or {})
+        if search is not None:
+            mcts_kwargs["search"] = search
         self.mcts = mcts_class(game_class=self.game_class, n_simulations=self.n_simulations, nn_model=search_net,
-                         cpuct=self.c_puct, add_dirichlet_noise=False, **(mcts_kwargs or {}))
+                         cpuct=self.c_puct, add_dirichlet_noise=False, **mcts_kwargs)
 
     def play(self, board, turn_number, last_opponent_move):
         game = self.game_class(size=self.board_size)

@@ -136,7 +136,7 @@ def selfplay_games(model, game_class, n_games: int, n_simulations: int, cpuct: f
                    dirichlet_alpha: float, dirichlet_epsilon: float, dirichlet_n_moves: int,
                    add_dirichlet_noise: bool = True, max_moves: int = 225, use_symmetries: bool = True,
                    board_size: int = 15, driver: Optional[BatchedSelfPlay] = None, native: bool = True,
-                   seeds=None, playout_cap=None):
+                   seeds=None, playout_cap=None, search: str = "reference"):
     """n_games concurrent self-play games (train.py:671-742 semantics per game).
     Returns (examples, winners {0,1,2: count}, driver).
 
@@ -146,9 +146,16 @@ def selfplay_games(model, game_class, n_games: int, n_simulations: int, cpuct: f
     drawing from numpy's global RNG.
 
     playout_cap=(p_full, fast_sims): playout cap randomization (NativeSelfPlay); the
-    examples are then 4-tuples ending in the policy weight.  Native driver only."""
+    examples are then 4-tuples ending in the policy weight.  Native driver only.
+
+    search="reference" (default; the reference's search, which never reads the value head) or
+    "alphazero" (value backup under virtual loss; native driver only)."""
     examples: List[Example] = []
     winners = {0: 0, 1: 0, 2: 0}
+    from _native_mcts import search_mode
+    if search_mode(search) and not native:
+        raise ValueError('search="alphazero" needs the native self-play driver (native=True): the Python '
+                         "generator search is the reference search only")
     if playout_cap is not None and not native:
         raise ValueError("playout_cap needs the native self-play driver (native=True): the Python "
                          "generator search has no per-move budget")
@@ -156,7 +163,7 @@ def selfplay_games(model, game_class, n_games: int, n_simulations: int, cpuct: f
         from mcts.native_mcts import NativeSelfPlay
         kw = dict(cpuct=cpuct, dirichlet_alpha=dirichlet_alpha, epsilon=dirichlet_epsilon,
                   apply_dirichlet_n_first_moves=dirichlet_n_moves, add_dirichlet_noise=add_dirichlet_noise,
-                  playout_cap=playout_cap)
+                  playout_cap=playout_cap, search=search)
         if hasattr(model, "board_evaluator"):      # HIP model: int8 leaves, GPU encode, pipelined groups
             driver = NativeSelfPlay(None, game_class, n_games, n_simulations,
                                     evaluator_factory=model.board_evaluator, groups=2 if n_games > 1 else 1, **kw)

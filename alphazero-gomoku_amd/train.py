@@ -64,12 +64,21 @@ def eval_game_gen(mcts_new, mcts_best, game, new_starts: bool):
 
 def evaluate_models(model_new: PyTorchModel, model_best: PyTorchModel, game_name: str = "gomoku",
                     n_games: int = 20, n_simulations: int = 100, cpuct: float = 1.0,
-                    native: bool = True, record: Optional[list] = None) -> Tuple[int, float, int]:
+                    native: bool = True, record: Optional[list] = None,
+                    search="reference") -> Tuple[int, float, int]:
     """(new_wins, win_rate, draws) over n_games (sharded across ranks), each opened
     by one random move in the centre 9x9 (train.py:440-445), new model first on
     even game indices.  native=True: both searches in C++ (mcts/native_mcts.NativeEval);
     native=False: Python searches under BatchedSelfPlay.  ``record`` (optional list)
-    receives this rank's finished games."""
+    receives this rank's finished games.  ``search``: "reference", "alphazero" or
+    {"new": mode, "best": mode} (NativeEval); the Python searches are the reference search only."""
+    from _native_mcts import search_mode
+    modes = search if isinstance(search, dict) else {"new": search, "best": search}
+    if set(modes) != {"new", "best"}:
+        raise ValueError(f'search must be a mode or {{"new": mode, "best": mode}}, got {search!r}')
+    if any([search_mode(m) for m in modes.values()]) and not native:
+        raise ValueError('search="alphazero" needs the native evaluation driver (native=True): the Python '
+                         "generator search is the reference search only")
     size = model_new.board_size
     center, radius = size // 2, 4
     games, starts, winners, failure = [], [], [], None
@@ -79,7 +88,7 @@ def evaluate_models(model_new: PyTorchModel, model_best: PyTorchModel, game_name
         games.append(game)
         starts.append(i % 2 == 0)
     try:
-        winners = _play_eval_games(model_new, model_best, games, starts, n_simulations, cpuct, native)
+        winners = _play_eval_games(model_new, model_best, games, starts, n_simulations, cpuct, native, modes)
     except Exception as e:   # every rank must still reach the collective below
         failure, winners = e, []
     fault = isinstance(failure, TowerFault)
@@ -99,7 +108,7 @@ def evaluate_models(model_new: PyTorchModel, model_best: PyTorchModel, game_name
     return new_wins, new_wins / float(n_games), draws
 
 
-def _play_eval_games(model_new, model_best, games, starts, n_simulations, cpuct, native):
+def _play_eval_games(model_new, model_best, games, starts, n_simulations, cpuct, native, search="reference"):
     if not games:
         winners = []
     elif native:
@@ -108,10 +117,10 @@ def _play_eval_games(model_new, model_best, games, starts, n_simulations, cpuct,
             # HIP models: int8 leaves, on-GPU encoding, both networks' batches in flight
             arena = NativeEval(None, GameClass, len(games), n_simulations, cpuct=cpuct,
                                evaluator_factories={"new": model_new.board_evaluator,
-                                                    "best": model_best.board_evaluator})
+                                                    "best": model_best.board_evaluator}, search=search)
         else:
             arena = NativeEval({"new": model_new.predict, "best": model_best.predict}, GameClass, len(games),
-                               n_simulations, cpuct=cpuct)
+                               n_simulations, cpuct=cpuct, search=search)
         winners = arena.play(games, ["new" if s else "best" for s in starts])
     else:
         gens = []
@@ -217,7 +226,7 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                     score_max_examples: int = 4096, history: Optional[list] = None,
                     ema_decay: Optional[float] = None, surprise_weight: Optional[float] = None,
                     playout_cap_prob: Optional[float] = None, playout_cap_fast_sims: Optional[int] = None,
-                    average_duplicates: bool = False, **reference_worker_kwargs):
+                    average_duplicates: bool = False, search: str = "reference", **reference_worker_kwargs):
     """Reference train.py:575-845.  `reference_worker_kwargs` (selfplay_num_workers,
     selfplay_device, ..., eval_torch_threads) are accepted for drop-in use and
     ignored: concurrency comes from batching games on the GPU.
@@ -296,7 +305,15 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
     buffer pickle and the sidecars keep the raw targets.  history entries carry
     "buffer_groups": {"positions", "groups", "largest"} of the buffer the iteration trained
     on, None when off.  No effect on playing strength has been measured.  False, the default,
-    makes none of these calls."""
+    makes none of these calls.
+
+    search ("reference" or "alphazero"): the tree search of self-play and of both gating
+    players.  "reference", the default, is the reference's search bit for bit -- it never
+    reads the value head, so the value the loop trains cannot change a move.  "alphazero" backs
+    every leaf's value up under virtual loss and re-mixes root noise at every noisy move
+    (include/azg_mcts.h).  history entries carry "search"."""
+    from _native_mcts import search_mode
+    search_mode(search)   # ValueError on an unknown mode, before anything is built
     if average_duplicates and not device_buffer:
         raise ValueError("average_duplicates needs device_buffer=True (the host ReplayBuffer does not merge positions)")
     if (playout_cap_prob is None) != (playout_cap_fast_sims is None):
@@ -378,6 +395,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             if selfplay_precision not in (None, "exact"):
                 model_candidate.set_eval_precision(selfplay_precision)
             cap_kw = {} if playout_cap is None else {"playout_cap": playout_cap}
+            if search != "reference":
+                cap_kw["search"] = search
             examples, winners, drv = selfplay_games(sp_model, GameClass, n_local, n_simulations, cpuct, temp_fn,
                                                     dirichlet_alpha, dirichlet_epsilon, dirichlet_n_moves,
                                                     max_moves=max_moves, board_size=board_size,
@@ -440,7 +459,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
                             "playout_cap": None if playout_cap is None else
                             {"p_full": playout_cap[0], "fast_sims": playout_cap[1],
                              "full_moves": drv.full_moves, "fast_moves": drv.fast_moves},
-                            "buffer_groups": buffer.duplicate_stats() if average_duplicates else None})
+                            "buffer_groups": buffer.duplicate_stats() if average_duplicates else None,
+                            "search": search})
 
         te = time.time()
         # with EMA on, the gated net is the average of the candidate's weights, not its last step
@@ -449,7 +469,8 @@ def train_alphazero(game_name: str = "gomoku", board_size: int = 15, num_iterati
             ev_new, ev_best = ((gated, model_best) if eval_symmetry is None else
                                (gated.symmetric(eval_symmetry), model_best.symmetric(eval_symmetry)))
             new_wins, win_rate, draws = evaluate_models(ev_new, ev_best, game_name, n_games=eval_games,
-                                                        n_simulations=eval_mcts_simulations, cpuct=cpuct)
+                                                        n_simulations=eval_mcts_simulations, cpuct=cpuct,
+                                                        **({} if search == "reference" else {"search": search}))
         except TowerFault:
             # a forward that computed on stale inputs and could not be recomputed: an
             # engine fault, not a lost evaluation -- never counted as a rejection
