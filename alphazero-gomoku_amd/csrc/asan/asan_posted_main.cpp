@@ -100,10 +100,33 @@ static void posted_state()
     p.trip(100.0, 30);
     for (unsigned i = 0; i < kStatusWords; ++i) w[i] = i + 1;
     p.clear();
-    for (unsigned i = 0; i < kStatusWords; ++i) CHECK(w[i] == 0);   // kTrainFlag included
+    // the two rings and the skip count are zeroed; the other train words are not clear()'s
+    for (unsigned i = 0; i < 2 * kTowerRing; ++i) CHECK(w[i] == 0);
+    for (unsigned i = 2 * kTowerRing; i < kStatusWords; ++i)
+        CHECK(w[i] == (i == 2 * kTowerRing + kTrainSkips ? 0u : i + 1));
     CHECK(p.count() == 0 && p.train_skips() == 0);
     CHECK(!p.breaker_open(100.0));      // and the breaker is closed
     CHECK(p.breaker_trips == 1 && p.seq == c && p.record(c));
+}
+
+// clear() while a train step is in flight: the step's overflow flag is not clear()'s to drop
+static void clear_leaves_the_step_in_flight_alone()
+{
+    unsigned w[kStatusWords];
+    PostedLaunches p;
+    p.attach(w, w);
+    const unsigned a = p.begin(call_of(1), true, 0), b = p.begin(call_of(1), true, 0);
+    w[a] = a;                                      // a timed-out launch
+    w[kTowerRing + b] = b;                         // a range overflow
+    w[2 * kTowerRing + kTrainFlag] = 1;            // set by the split-fp16 forward of a queued step
+    w[2 * kTowerRing + kTrainSkips] = 3;
+    p.trip(50.0, 30);
+    CHECK(p.count() == 2 && p.train_skips() == 3 && p.breaker_open(51.0));
+    p.clear();
+    CHECK(p.posted(a) == 0 && p.posted(b) == 0 && p.count() == 0 && p.train_skips() == 0);
+    CHECK(w[2 * kTowerRing + kTrainFlag] == 1);    // only kTrainFlag survives
+    for (unsigned i = 0; i < kStatusWords; ++i) CHECK(w[i] == (i == 2 * kTowerRing + kTrainFlag ? 1u : 0u));
+    CHECK(!p.breaker_open(51.0));                  // the breaker is closed
 }
 
 static void breaker_and_counters()
@@ -141,6 +164,7 @@ int main()
 {
     sequence_numbers_and_slots();
     posted_state();
+    clear_leaves_the_step_in_flight_alone();
     breaker_and_counters();
     if (fails) {
         std::fprintf(stderr, "asan_posted: %d check(s) failed\n", fails);

@@ -196,6 +196,7 @@ struct TowerPlan {
     unsigned seq = 0;         // the launch's number (0: not posted)
     bool fp16 = false;        // the one-product fp16 precision (variant 14 with one product)
     bool recompute = false;   // azg_pv_recover's rerun: must not wait across workgroups
+    bool unsplit = false;     // the breaker is open: variant 14 runs one workgroup per board (no exchange waits)
 };
 
 // The heads' 1x1 projection weights and folded BN: policy (2 channels) then value (1), contiguous.
@@ -234,6 +235,15 @@ static int32_t next_b16_split(azg_pv* h, hipStream_t st, Board16Split* sp)
     return 0;
 }
 
+// True when board_tower runs some board of a variant-14 launch of `images` split (the whole
+// small batch, or the last partial round): the launches that wait across workgroups.
+static bool board16_would_split(int images)
+{
+    const int smax = board16_split_max(), grid = board16_grid();
+    if (images > 0 && images <= smax) return true;
+    return images > grid && grid > 0 && images % grid != 0 && images % grid <= smax;
+}
+
 // The board-resident tower (pv_board.hip, pv_board16.hip; variants 13 and 14): every conv of
 // one board from LDS, the tower output in place over the stem output in act[0].
 static int32_t board_tower(azg_pv* h, int images, hipStream_t st, const TowerPlan& p)
@@ -242,11 +252,12 @@ static int32_t board_tower(azg_pv* h, int images, hipStream_t st, const TowerPla
     const int* off = h->conv_bn_off.data();
     float* X = h->act[0];
     // EVAL_ARITH = 2: small batches run split (three workgroups per board, heads unfused; not
-    // for a recompute, which must not wait across workgroups), the rest one workgroup per
-    // board with the heads' projections fused (features into hbuf, forward_eval)
+    // for a recompute or under an open breaker, which must not wait across workgroups), the
+    // rest one workgroup per board with the heads' projections fused (features into hbuf,
+    // forward_eval)
     // a one-workgroup launch of B = k * grid + r boards ends with r boards on r CUs: for
     // r <= BOARD16_SPLIT_MAX those r run split after the k full rounds (their heads projected here)
-    const int smax = b16 && !p.recompute ? board16_split_max() : 0;
+    const int smax = b16 && !p.recompute && !p.unsplit ? board16_split_max() : 0;
     const int grid = b16 ? board16_grid() : 0;
     const int tail = b16 && images > grid && grid > 0 && images % grid <= smax ? images % grid : 0;
     h->b16_split = b16 && images <= smax;
@@ -440,12 +451,19 @@ int32_t forward_eval(azg_pv* h, const EvalCall& c, hipStream_t st, const EvalOpt
     if (p.h3)
         if (int32_t r = ensure_h3(h, st, p.fp16)) return r;
     // EVAL_ARITH = 2 at C = 128: the 16x16x32 board tower is the one form of its arithmetic, for
-    // every batch and path (it has no cross-workgroup waits: nothing for the breaker to avoid;
-    // known defect, ADVICE.md: its split form does wait and still ignores the breaker)
+    // every batch and path.  One workgroup per board it waits on no other workgroup; its split
+    // form (small batches, a launch's last partial round) exchanges boundary rows and does.
     const bool k32 = p.fp16 || (p.h3 && g_tower_h3 == 2 && C == 128 && h->NB <= kTowerMaxBlocks);
     p.variant = k32 ? 14 : o.per_layer ? 0 : tower_variant(h, c, st, p.h3);
-    if (p.variant != 0 && !k32 && h->posted.breaker_open(now_s())) {
-        p.variant = 0;
+    // an open breaker keeps the forward off every cross-workgroup wait: per-layer convs, or
+    // for the 16x16x32 board tower one workgroup per board.  breaker_launches counts the
+    // forwards it changed: a board16 launch that would not have split runs as it always does
+    if (p.variant != 0 && !o.per_layer && (!k32 || board16_would_split(c.images())) &&
+        h->posted.breaker_open(now_s())) {
+        if (k32)
+            p.unsplit = true;
+        else
+            p.variant = 0;
         ++h->posted.breaker_launches;
     }
     // a tower or H3 launch gets a number and a record of its call (azg_pv_recover);

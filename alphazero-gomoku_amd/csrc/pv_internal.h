@@ -94,7 +94,7 @@ extern int g_h3_tower_var;
 extern unsigned g_tower_wait_us;
 extern int g_board_abl;        // pv_board.hip (read by the study build only)
 extern int g_board16_split;    // pv_board16.hip
-extern int g_tower_breaker_s;  // pv_eval.hip: seconds of per-layer convs after a recovered launch
+extern int g_tower_breaker_s;  // pv_eval.hip: seconds without cross-workgroup waits after a recovered launch
 extern int g_train_fuse_apply; // pv_train.hip
 extern int g_train_fuse_fin;
 extern int g_train_apply_grid;

@@ -65,10 +65,11 @@ struct PostedLaunches {
     uint32_t recovered = 0;              // launches recomputed per layer
     uint32_t h3_overflows = 0;           // launches recomputed with fp32 MFMA (activations beyond fp16's range)
     // circuit breaker: a recovered launch means the dispatch did not run as one (the GPU is
-    // shared and parts of it were suspended); forwards run per-layer convs until then
+    // shared and parts of it were suspended); until then forwards wait on no other workgroup
+    // (per-layer convs; the 16x16x32 board tower one workgroup per board)
     double breaker_until = 0.0;          // steady-clock seconds (0: closed)
     uint32_t breaker_trips = 0;
-    uint32_t breaker_launches = 0;       // forwards that ran per layer because of it (the caller counts)
+    uint32_t breaker_launches = 0;       // forwards it changed: per layer, or board16 unsplit (the caller counts)
 
     static unsigned slot(unsigned s) { return s & (kTowerRing - 1); }
     static unsigned load(const unsigned* w) { return __atomic_load_n(w, __ATOMIC_ACQUIRE); }
@@ -135,10 +136,16 @@ struct PostedLaunches {
 
     void clear()
     {
-        // every word, kTrainFlag of a train step in flight included (azg_pv_clear_status wipes kTrainFlag)
-        if (ring_host)
-            for (unsigned i = 0; i < kStatusWords; ++i) zero(ring_host + i);
-        breaker_until = 0.0;   // and the per-layer breaker closes
+        // the two rings and the skip count.  Not kTrainFlag: it belongs to a train step that may
+        // still be queued, whose heads_small_grads moves it into the skip slot and clears it.
+        // (A step whose host code fails between the forward that set the flag and
+        // heads_small_grads leaves it set: the next step is then skipped and redone in fp32
+        // once -- the safe direction -- and clears it.)
+        if (ring_host) {
+            for (unsigned i = 0; i < 2 * kTowerRing; ++i) zero(ring_host + i);
+            zero(ring_host + 2 * kTowerRing + kTrainSkips);
+        }
+        breaker_until = 0.0;   // and the breaker closes
     }
 
     // true while the breaker is open; at its expiry it closes itself

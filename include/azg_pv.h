@@ -461,11 +461,12 @@ enum azg_pv_tuning_key {
      * the XCD's L2, +2 % at B = 512 and 4096, measured; 0 = one 128x64 tile per
      * claim); bitwise identical results */
     AZG_PV_TUNE_TOWER_CLAIM = 17,
-    /* seconds a handle runs per-layer convs after azg_pv_recover recomputed one of its
-     * tower launches (default 30; 0 disables the breaker).  A timed-out wait means
-     * parts of the dispatch were suspended while others ran (the GPU is shared with
-     * another process); per-layer launches have no
-     * cross-workgroup waits */
+    /* seconds a handle keeps off cross-workgroup waits after azg_pv_recover recomputed
+     * one of its timed-out launches (default 30; 0 disables the breaker): the tile towers
+     * give way to per-layer convs, and the 16x16x32 board tower (key 19 = 2, the fp16
+     * precision) runs one workgroup per board instead of its split form.  A timed-out
+     * wait means parts of the dispatch were suspended while others ran (the GPU is
+     * shared with another process) */
     AZG_PV_TUNE_BREAKER_SECONDS = 18,
     /* eval residual-conv arithmetic: 2 (default) and 1 split-fp16 -- every fp32 operand
      * x is split into hi = fp16(x), lo = fp16(x - hi) and a product is lo*hi + hi*lo +
@@ -569,7 +570,10 @@ int32_t azg_pv_recover(azg_pv* h, uint32_t seq, int32_t* recovered, void* stream
  * both not yet recovered (0: nothing to settle).  The Python layer raises on a posted
  * launch it cannot recover (its buffers are gone).  azg_pv_clear_status drops every
  * posted launch without recomputing it, zeroes the skipped-step count and closes the
- * per-layer breaker (key 18). */
+ * breaker (key 18).  It leaves the overflow flag of a train step in flight alone: a step
+ * still queued when it is called is skipped or committed as if it had not been called
+ * (a train call that failed on the host after its forward had set the flag leaves it to
+ * the next step, which is then skipped once). */
 int32_t azg_pv_status(const azg_pv* h);
 int32_t azg_pv_posted(const azg_pv* h, uint32_t seq);
 int32_t azg_pv_clear_status(azg_pv* h);
@@ -608,8 +612,8 @@ typedef struct {
     int32_t producer_start_us;  /* its start relative to the wait's start */
     uint32_t max_wall_us;       /* longest WALL time of a wait (awake + suspended) */
     uint32_t waits_suspended;   /* waits whose wall time exceeded their awake time by > 1 ms */
-    uint32_t breaker_trips;     /* recoveries that switched the handle to per-layer convs (key 18) */
-    uint32_t breaker_launches;  /* forwards run per layer while the breaker was open */
+    uint32_t breaker_trips;     /* recoveries that opened the breaker (key 18) */
+    uint32_t breaker_launches;  /* forwards the open breaker changed: per layer, or board16 unsplit */
     uint32_t h3_overflows;      /* split-fp16 forwards recomputed with fp32 MFMA (key 19: an activation
                                    beyond fp16's range, 65504) */
     uint32_t train_h3_overflows;   /* train steps skipped because a split-fp16 train forward (key 49) met an

@@ -589,7 +589,10 @@ def test_board16_split_bitwise_equals_one_workgroup(B):
     exchange their conv outputs' boundary rows through L2, and a larger launch's last partial
     round (B = 300: 256 + 44) runs that way after the full rounds: bitwise the one-workgroup
     tower (same per-wave tiles and MFMA chains).  A timed-out exchange wait (key 14 = 0) posts
-    the launch and predict recomputes it unsplit -- bitwise again."""
+    the launch and predict recomputes it unsplit -- bitwise again.  The recovery opens the
+    breaker (key 18 = 30 s): with key 14 still 0, where a split launch would time out at once,
+    the next forward runs one workgroup per board -- bitwise, nothing posted, no recovery, no
+    new timeout, one breaker launch.  clear_status closes the breaker."""
     import _native
     lib = _native.load_library()
     m = make_model(6, 128, seed=12)
@@ -598,6 +601,7 @@ def test_board16_split_bitwise_equals_one_workgroup(B):
     bi8, pl8 = np.asarray(boards, np.int8).reshape(B, 225), np.asarray(players, np.int8)
     x = encode_batch(boards, players)
     prev = lib.azg_pv_set_tuning(TUNE.BOARD16_SPLIT_MAX, 0)
+    prev_breaker = lib.azg_pv_set_tuning(TUNE.BREAKER_SECONDS, 30)
     try:
         p0, v0 = m.predict_boards(bi8, pl8)
         q0, w0 = m.predict(x)
@@ -611,10 +615,28 @@ def test_board16_split_bitwise_equals_one_workgroup(B):
         lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, 0)
         try:
             p2, v2 = m.predict_boards(bi8, pl8)
+            assert np.array_equal(p2, p0) and np.array_equal(v2, v0)
+            d = eng.tower_diag()
+            assert eng.recoveries == r0 + 1 and d["timeouts"] > 0
+            eng.check_status()
+            # the breaker is open and every exchange wait would still time out at once
+            assert d["breaker_trips"] == 1 and d["breaker_launches"] == 0, d
+            p3, v3 = m.predict_boards(bi8, pl8)
+            assert np.array_equal(p3, p0) and np.array_equal(v3, v0)
+            d3 = eng.tower_diag()
+            assert eng.recoveries == r0 + 1, "the forward behind a recovered split launch ran split again"
+            assert d3["timeouts"] == d["timeouts"] and d3["breaker_launches"] == 1, (d, d3)
+            assert d3["breaker_trips"] == 1 and lib.azg_pv_status(eng.h) == 0
         finally:
             lib.azg_pv_set_tuning(TUNE.TOWER_WAIT_US, -1)
-        assert np.array_equal(p2, p0) and np.array_equal(v2, v0)
-        assert eng.recoveries == r0 + 1 and eng.tower_diag()["timeouts"] > 0
+        # breaker closed, waits healthy: bitwise again, nothing posted, not a breaker launch
+        eng.clear_status()
+        p4, v4 = m.predict_boards(bi8, pl8)
+        d4 = eng.tower_diag()
+        assert np.array_equal(p4, p0) and np.array_equal(v4, v0)
+        assert eng.recoveries == r0 + 1 and lib.azg_pv_status(eng.h) == 0
+        assert d4["timeouts"] == d["timeouts"] and d4["breaker_launches"] == 1, (d, d4)
         eng.check_status()
     finally:
+        lib.azg_pv_set_tuning(TUNE.BREAKER_SECONDS, prev_breaker)
         lib.azg_pv_set_tuning(TUNE.BOARD16_SPLIT_MAX, prev)

@@ -315,21 +315,41 @@ def test_fp16_range_guard_recomputes_in_fp32():
 # ---------------------------------------------------------------- 6. timed-out split launch
 def test_fp16_timed_out_split_launch_is_rerun_in_fp16():
     """Key 14 = 0 makes the split form's exchange waits time out at once: the launch is
-    posted and recover reruns it with one workgroup per board in fp16 (run once)."""
+    posted and recover reruns it with one workgroup per board in fp16 (run once).  The recovery
+    opens the breaker (key 18 = 30 s): with key 14 still 0 the next forward runs one workgroup
+    per board in fp16 -- bitwise, no recovery, no new timeout, one breaker launch -- and after
+    clear_status, with healthy waits, the forward is bitwise again and posts nothing."""
     lib = _lib()
     m, boards, players, x, p300, v300 = _mode_case()
     eng = m.engine
     bi8, pl8 = _i8(boards[:3], players[:3])
     with keys(lib, {K.BOARD16_SPLIT_MAX: 0}):
         p0, v0 = m.predict_boards(bi8, pl8)
+    eng.clear_status()
     eng.tower_diag_clear()
     r0 = eng.recoveries
-    with keys(lib, {K.TOWER_WAIT_US: 0}):
-        p1, v1 = m.predict_boards(bi8, pl8)
     try:
-        assert eng.recoveries == r0 + 1 and eng.tower_diag()["timeouts"] > 0
-        assert np.array_equal(p1, p0) and np.array_equal(v1, v0)
-        eng.check_status()
+        with keys(lib, {K.BREAKER_SECONDS: 30}):
+            with keys(lib, {K.TOWER_WAIT_US: 0}):
+                p1, v1 = m.predict_boards(bi8, pl8)
+                d = eng.tower_diag()
+                assert eng.recoveries == r0 + 1 and d["timeouts"] > 0
+                assert np.array_equal(p1, p0) and np.array_equal(v1, v0)
+                eng.check_status()
+                assert d["breaker_trips"] == 1 and d["breaker_launches"] == 0, d
+                p2, v2 = m.predict_boards(bi8, pl8)
+                d2 = eng.tower_diag()
+                assert np.array_equal(p2, p0) and np.array_equal(v2, v0)
+                assert eng.recoveries == r0 + 1, "the forward behind a recovered split launch ran split again"
+                assert d2["timeouts"] == d["timeouts"] and d2["breaker_launches"] == 1, (d, d2)
+                assert d2["breaker_trips"] == 1 and lib.azg_pv_status(eng.h) == 0
+            eng.clear_status()
+            p3, v3 = m.predict_boards(bi8, pl8)
+            d3 = eng.tower_diag()
+            assert np.array_equal(p3, p0) and np.array_equal(v3, v0)
+            assert eng.recoveries == r0 + 1 and lib.azg_pv_status(eng.h) == 0
+            assert d3["timeouts"] == d["timeouts"] and d3["breaker_launches"] == 1, (d, d3)
+            eng.check_status()
     finally:
         eng.clear_status()
         eng.tower_diag_clear()

@@ -36,16 +36,22 @@ def weighted_loss(logits, value, pi, z, wp=None, wv=None):
     return (wp * kl).sum() / B, (wv * sq).sum() / B
 
 
-def weighted_masked_grads_fp64(state: dict, blocks: int, channels: int, x, pi, z, masks: dict, wp=None, wv=None):
-    """(grads {name: float64 ndarray}, (policy_loss, value_loss)) of the weighted loss with
-    the caller's ReLU masks."""
-    net = RefNet(blocks, channels).double()
+def weighted_masked_grads_fp64(state: dict, blocks: int, channels: int, x, pi, z, masks: dict, wp=None, wv=None,
+                               return_pre: bool = False, dtype=torch.float64):
+    """(grads {name: ndarray}, (policy_loss, value_loss)) of the weighted loss with the
+    caller's ReLU masks; with return_pre the pre-activations of every masked ReLU come third
+    (as oracle.ref_net.masked_grads_fp64 returns them).  dtype: the arithmetic of the whole
+    run; torch.float32 gives the fp32 run a tolerance is measured with."""
+    net = RefNet(blocks, channels).to(dtype)
     load_numpy_state(net, state)
     net.train()
-    logits, value, _ = masked_forward_fp64(net, x, masks)
+    logits, value, pre = masked_forward_fp64(net, x, masks, dtype=dtype)
     pl, vl = weighted_loss(logits, value, pi, z, wp, wv)
     (pl + vl).backward()
-    return {n: q.grad.numpy() for n, q in net.named_parameters()}, (float(pl.detach()), float(vl.detach()))
+    out = ({n: q.grad.numpy() for n, q in net.named_parameters()}, (float(pl.detach()), float(vl.detach())))
+    if return_pre:
+        out += ({k: v.detach().numpy() for k, v in pre.items()},)
+    return out
 
 
 def own_masks_fp64(state: dict, blocks: int, channels: int, x) -> dict:
